@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: exact k-NN QPS@k=10 on the Cohere-shaped corpus (BASELINE.json config C3).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N)
 
 Workload (config C3): 10,000,000 × 768 fp32 vectors, COSINE, 8 index shards of
@@ -17,8 +17,16 @@ C-ABI call per rank (osk_shards_search_merge_device; libosknn owns the RCCL comm
 value = queries answered by the whole job per second.  Queries are issued as a serving node's search
 threads issue them: F = 4 in flight (--inflight), each a separate single-query C-ABI call on its own
 stream with its own view (workspace) over the shared segments, round-robin — one query's settle, merge
-and exchange run under the next one's scan instead of idling the chip.  The same run also times the
-steps strictly one after another ("one_in_flight": per-query latency).
+and exchange run under the next one's scan instead of idling the chip.
+
+A plain run does only what `value` needs: it stages the corpus, warms up, times the K steps, writes the last
+timed step's outputs if `--dump-outputs DIR` is given (DIR/<name>.npy: what a caller of the step receives,
+as float32 / float64; the inputs are the same from run to run) and prints the result line.  `--full` adds
+everything else the benchmark measures or checks, each in a pass of its own after the timed steps: the same
+steps strictly one after another ("one_in_flight": per-query latency, and the scan kernel's isolated launch
+time for the roofline), the fp32 streaming scan with its bit-for-bit comparison, the committed PMC traffic
+and read-ceiling figures, and the CPU baseline.  The paragraphs below that describe those figures describe
+a `--full` run.
 
 Path (the library's own choice): a single unfiltered query — the headline —
 takes the certified prefilter's 6-bit tier (sq6_pilot seeds per-shard floors from 1 % of the rows on the int8
@@ -216,6 +224,28 @@ def _cpu_baseline_pinned(O, sample_rows, n_queries, threads, passes, isa, node, 
     }
 
 
+OUTPUT_NAMES = ("scores", "docs", "shard", "count", "total", "max_score")
+DUMP_MAX_BYTES = 48 << 20   # of array data, all files together
+
+
+def dump_outputs(path: str, arrays) -> None:
+    """The arrays a caller of the timed step receives (the last timed step's), as DIR/<name>.npy: float
+    scores stay float32, the integer outputs (doc IDs, shard indices, counts, total hits) go to float64,
+    which holds every value of theirs exactly.  A few hundred bytes at the headline's batch 1; beyond
+    DUMP_MAX_BYTES in all (huge --batch × --k) the same seeded sample of the batch's queries is kept in every
+    array, and `rows.npy` names the queries kept."""
+    os.makedirs(path, exist_ok=True)
+    arrays = [arr.astype(np.float32 if arr.dtype == np.float32 else np.float64) for arr in arrays]
+    nq = len(arrays[0])
+    per_query = sum(arr.nbytes // max(1, nq) for arr in arrays) + 8
+    if nq * per_query > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_MAX_BYTES // per_query, replace=False))
+        arrays = [arr[rows] for arr in arrays]
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    for name, arr in zip(OUTPUT_NAMES, arrays):
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     global K, SIZE
     ap = argparse.ArgumentParser()
@@ -233,7 +263,14 @@ def main():
     ap.add_argument("--inflight", type=int, default=4,
                     help="queries in flight: search threads issuing round-robin, each on its own stream with its "
                          "own view (workspace) over the shared segments; 1 = strictly one query after another")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the one-in-flight pass (latency, isolated scan-launch "
+                         "roofline), the fp32 streaming scan and its bit-for-bit comparison with the prefilter, "
+                         "the committed PMC traffic / read-ceiling figures and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the outputs of the last timed step to DIR/<name>.npy (scores, docs, "
+                         "shard, count, total, max_score; float32 or float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline leg")
     ap.add_argument("--profile-every", type=int, default=8,
                     help="stamp the scan launches of every N-th search with HIP events (osk_view_profile N); the "
                          "stamps cost a few µs of stream time around the stamped launch, so the timed loop samples")
@@ -390,15 +427,21 @@ def main():
     fb0, rs0, calls0 = counter("sq8_fallback_queries"), counter("sq8_rescored_rows"), counter("sq8_calls")
     sel0, six0, rb0 = counter("select_calls"), counter("sq6_calls"), counter("sq6_rebound_rows")
     elapsed_max, ovl_scan_ms, ev_ms, out = timed(a.steps, a.warmup)
+    # the last timed step's outputs, copied before any later pass overwrites the preallocated buffers
+    last = [t.cpu().numpy().copy() for t in out]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
     # The same steps one at a time (one query in flight): the per-query latency, and the scan kernel's
     # isolated launch duration — the roofline's denominator.  With F > 1 the launches of neighbouring
     # queries overlap on the device and share HBM, so their individual durations overstate the kernel's
     # time; the whole step's sustained rate is reported beside it.
     n_lat = min(a.steps, 50)
-    if F > 1:
-        lat_el, scan_avg_ms, _, _ = timed(n_lat, 2, slots=1)
-    else:
+    if F == 1:
         lat_el, scan_avg_ms, n_lat = elapsed_max, ovl_scan_ms, a.steps
+    elif a.full:
+        lat_el, scan_avg_ms, _, _ = timed(n_lat, 2, slots=1)
+    else:   # a plain run: no pass of its own for the isolated launch time
+        lat_el, scan_avg_ms = None, None
     # the path the library chose (prefilter searches count sq8_calls, select-path searches select_calls;
     # else bf16×3 from batch 96, else fp32)
     prefilter = counter("sq8_calls") > calls0
@@ -407,7 +450,7 @@ def main():
     batched = not prefilter and not select and B >= 96 and K <= 12
     sq8_mfma = prefilter and sq8_mfma_min > 0 and B >= sq8_mfma_min
     # sanity on the last step: every query got `SIZE` hits from the 10M corpus
-    cnt = out[3].cpu().numpy()
+    cnt = last[3]
     assert np.all(cnt == SIZE), cnt
 
     u8 = (DIM + 15) // 16
@@ -443,8 +486,8 @@ def main():
         passes = (B + 7) // 8
         bytes_per_launch = rows_local * DIM * 4 * passes
         kernel_name = "scan_f32<L=16,V=12,NQ=min(B,8),dot,nt>"
-    achieved = bytes_per_launch / (scan_avg_ms * 1e-3) / 1e9
-    mfma_tflops = (3 * 2 * B * rows_local * DIM) / (scan_avg_ms * 1e-3) / 1e12 if batched else None
+    achieved = bytes_per_launch / (scan_avg_ms * 1e-3) / 1e9 if scan_avg_ms else None
+    mfma_tflops = (3 * 2 * B * rows_local * DIM) / (scan_avg_ms * 1e-3) / 1e12 if batched and scan_avg_ms else None
 
     extra = {}
     if prefilter:
@@ -457,6 +500,7 @@ def main():
             "rescored_rows_per_query": (counter("sq8_rescored_rows") - rs0) / max(1, n_calls * B),
             "searches": n_calls,
         }
+    if prefilter and a.full:
         # the fp32 streaming scan on the same queries, same run: its own roofline, and the results
         # of both paths compared bit for bit (docs, scores, shard indices) on a sample of batches
         _lib.tune("sq8", 0)
@@ -493,8 +537,8 @@ def main():
                      shard=np.stack([o[2] for o in outs]), count=np.stack([o[3] for o in outs]),
                      total=np.stack([o[4] for o in outs]), max_score=np.stack([o[5] for o in outs]))
 
-    traffic, traffic_src = pmc_traffic(rows_local, B, prefilter, six)
-    ceiling = read_ceiling()
+    traffic, traffic_src = pmc_traffic(rows_local, B, prefilter, six) if a.full else (None, None)
+    ceiling = read_ceiling() if a.full else None
     if rank == 0:
         res = {
             "metric": "exact k-NN QPS@k=10 (recall=1.0), 10M×768 fp32, 1/2/4/8 GPUs; % HBM roofline",
@@ -521,14 +565,15 @@ def main():
                             else "one GPU: scan + device merge, no collective")
                            if a.exchange == "osk" else f"torch.distributed {a.dist_backend} all-gather + device merge"))},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                         "frac": achieved / HBM_PEAK_GBS if achieved else None, "traffic": traffic, "traffic_source": traffic_src,
                          "measured_read_ceiling_GBps": ceiling,
-                         "frac_of_measured_read_ceiling": achieved / ceiling if ceiling else None,
+                         "frac_of_measured_read_ceiling": achieved / ceiling if ceiling and achieved else None,
                          "read_ceiling_source": os.path.relpath(READ_CEILING, ROOT) if ceiling else None,
                          "kernel": kernel_name, "scan_ms_avg": scan_avg_ms,
-                         "scan_ms_measured_in": ("the one-in-flight pass of this run (isolated launches)" if F > 1
-                                                 else "the timed region")
-                         + f", every {max(1, a.profile_every)}th search's launch sampled",
+                         "scan_ms_measured_in": (("the one-in-flight pass of this run (isolated launches)" if F > 1
+                                                  else "the timed region")
+                                                 + f", every {max(1, a.profile_every)}th search's launch sampled")
+                         if scan_avg_ms is not None else "not measured: the one-in-flight pass runs with --full",
                          "sustained_GBps": bytes_per_launch / (elapsed_max / a.steps) / 1e9,
                          "sustained_frac": bytes_per_launch / (elapsed_max / a.steps) / 1e9 / HBM_PEAK_GBS,
                          "overlapped_scan_ms_avg": ovl_scan_ms if F > 1 else None,
@@ -536,10 +581,12 @@ def main():
                          "bf16_mfma_tflops": mfma_tflops},
             "gpu_event_ms_per_step": ev_ms / a.steps,
             "inflight": F,
+            "full": a.full,
         }
-        res["one_in_flight"] = {"value": n_lat * B / lat_el, "latency_ms_per_step": lat_el / n_lat * 1e3}
+        if lat_el is not None:
+            res["one_in_flight"] = {"value": n_lat * B / lat_el, "latency_ms_per_step": lat_el / n_lat * 1e3}
         res.update(extra)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # the GPU box grants 16 host threads per GPU (OMP_NUM_THREADS there); nproc shows the whole host
             threads = int(os.environ.get("OMP_NUM_THREADS", "0")) or min(16, os.cpu_count() or 1)
             res["cpu_baseline"] = cpu_baseline(a.cpu_sample_rows, a.cpu_queries, threads)
