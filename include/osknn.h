@@ -49,6 +49,10 @@
  *       S/search/internal/ContextIndexSearcher.java:203-218, the per-leaf TopDocs.merge(k, …)
  *       into the shard's top-k, and the shard collector's cut to from+size
  *       (S/search/query/TopDocsCollectorContext.java:866-891).
+ *   osk_seg_search_threshold / osk_view_search_threshold / osk_view_search_threshold_device
+ *       [L] AbstractVectorSimilarityQuery (FloatVectorSimilarityQuery, ByteVectorSimilarityQuery) over a
+ *       flat field: every accepted doc whose score is ≥ resultSimilarity, in doc order, with the exact
+ *       count — OpenSearch's k-NN `min_score`.
  *   osk_merge_device / osk_topdocs_merge
  *       The coordinator's reduce: S/action/search/SearchPhaseController.java:224-246 (mergeTopDocs →
  *       [L] TopDocs.merge(from, size, shardHits): score desc, then shardIndex asc, then doc asc),
@@ -290,7 +294,7 @@ int32_t osk_view_stats(osk_view* view, int64_t* batched_calls, int64_t* fallback
  * "sq8_fallback_queries" (queries where some tile's candidate
  * list overflowed past the certificate and the tile was re-scanned exactly), "sq8_exact_tiles"
  * (such tiles), "sq8_rescored_rows" (rows re-scored exactly, all calls), "select_calls" (searches
- * on the select path, k > 12), "host_slots" (workspace slots the host entries have leased: 1 + replicas),
+ * on the select path, k > 12), "threshold_calls" (similarity-threshold searches), "host_slots" (workspace slots the host entries have leased: 1 + replicas),
  * "host_batches" / "host_batched_requests" (opportunistic batching of concurrent host calls).  The
  * search counters sum over the view and the replica slots its host entries leased.  osk_view_profile /
  * osk_view_scan_time time the device-entry calls on this view object only (per-call host timing:
@@ -317,6 +321,51 @@ int32_t osk_view_search(osk_view* view, const void* queries, int32_t n_queries, 
                         int32_t from, int32_t size, const uint64_t* const* accept,
                         float* out_scores, int32_t* out_docs, int32_t* out_shard_index,
                         int32_t* out_count, int64_t* out_total_hits, float* out_max_score);
+
+/* ---- similarity-threshold (radial) search: every vector at least this similar ----
+ * [L] AbstractVectorSimilarityQuery (FloatVectorSimilarityQuery / ByteVectorSimilarityQuery) on a flat field:
+ * a doc matches iff it is accepted (AcceptDocs bit set, or no bitset) and its score ≥ resultSimilarity —
+ * OpenSearch's k-NN `min_score`.  Exact: one brute-force corpus pass.
+ *   min_scores   one threshold per query, in the score domain (after the VectorSimilarityFunction
+ *                transform: the values osk_seg_search returns).  A row is a hit iff
+ *                `score >= min_score` as an IEEE float comparison: NaN on either side is no hit
+ *                (a COSINE zero vector never matches), −0.0 and +0.0 compare equal.
+ *   scores       the device-order scores, bit-identical to the k-NN entries' for the same row.
+ *   order        hits come back in ascending doc order ([L] the query's scorer iterates by doc; a shard's
+ *                leaves in docBase order), with their scores.
+ *   cap          capacity per (query, shard): total = the exact number of hits whatever the capacity;
+ *                when total > cap the FIRST cap hits in doc order are returned (deterministic) and the
+ *                caller, who sees total, may call again with a larger cap.  cap ≥ 1.
+ *   unused slots past the returned count: doc = INT32_MAX, score = -inf (as osk_seg_search).
+ *   visited      number of accepted vectors scored, as in the k-NN entries.
+ * The shard's collector then sorts and cuts the hits (S/search/query/TopDocsCollectorContext.java:866-891:
+ * a TopScoreDocCollector over the scorer — score desc, doc asc, numDocs = from+size, totalHits = total).
+ * A null pointer, n_queries < 1 or cap < 1 is OSK_ERR_INVALID before the device is touched; without a
+ * device the entries return OSK_ERR_NO_DEVICE. */
+
+/* [L] FloatVectorSimilarityQuery / ByteVectorSimilarityQuery over ONE leaf — all hits of one segment, host
+ * buffers, synchronous; docs segment-local ascending.
+ *   out_docs/out_scores  n_queries × cap;  out_count[q] = min(total, cap);  out_total[q] exact
+ *   out_visited          (optional) n_queries */
+int32_t osk_seg_search_threshold(osk_seg* seg, const void* queries, int32_t n_queries,
+                                 const float* min_scores, const uint64_t* accept_bits, int32_t cap,
+                                 int32_t* out_docs, float* out_scores, int32_t* out_count,
+                                 int64_t* out_total, int64_t* out_visited);
+/* The same per shard of a view (the entry a VectorSimilarityCollector-style search of a whole shard binds
+ * to): host buffers, synchronous; docs shard-local (docBase added) ascending.
+ *   accept               NULL or n_segs host pointers (each NULL or a host bitset)
+ *   out_docs/out_scores  [n_queries][n_shards][cap];  out_count/out_total  [n_queries][n_shards] */
+int32_t osk_view_search_threshold(osk_view* view, const void* queries, int32_t n_queries,
+                                  const float* min_scores, const uint64_t* const* accept, int32_t cap,
+                                  int32_t* out_docs, float* out_scores, int32_t* out_count,
+                                  int64_t* out_total);
+/* The same with DEVICE buffers, asynchronous on `stream` under the view's mutex (the rules of
+ * osk_view_search_device: NULL = the library's stream; d_accept a device array of n_segs device pointers).
+ *   d_visited  optional out, n_segs int64 (accepted vectors scored per segment, per query) */
+int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, int32_t n_queries,
+                                         const float* d_min_scores, const uint64_t* const* d_accept,
+                                         int32_t cap, int32_t* d_docs, float* d_scores, int32_t* d_count,
+                                         int64_t* d_total, int64_t* d_visited, void* stream);
 
 /* [L] TopDocs.merge(from, size, shardHits) + TopDocsStats over host arrays (no device).
  *   shard_counts[s] hits of list s; shard_scores/shard_docs row s holds them at offset s*stride

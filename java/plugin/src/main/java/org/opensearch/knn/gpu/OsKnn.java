@@ -78,6 +78,25 @@ final class OsKnn {
     // int32_t osk_last_call_device_ns(int64_t* device_ns, int32_t* shared_by)
     static final MethodHandle LAST_CALL_NS = h("osk_last_call_device_ns", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
 
+    // Similarity-threshold search ([L] AbstractVectorSimilarityQuery on a flat field; k-NN min_score)
+    // int32_t osk_seg_search_threshold(osk_seg* seg, const void* queries, int32_t n_queries, const float* min_scores,
+    //     const uint64_t* accept_bits, int32_t cap, int32_t* out_docs, float* out_scores, int32_t* out_count,
+    //     int64_t* out_total, int64_t* out_visited)
+    static final MethodHandle SEG_SEARCH_THRESHOLD = h("osk_seg_search_threshold", FunctionDescriptor.of(JAVA_INT,
+        ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS),
+        Linker.Option.critical(true));   // heap arrays are passed directly
+    // int32_t osk_view_search_threshold(osk_view* view, const void* queries, int32_t n_queries,
+    //     const float* min_scores, const uint64_t* const* accept, int32_t cap, int32_t* out_docs, float* out_scores,
+    //     int32_t* out_count, int64_t* out_total)
+    static final MethodHandle VIEW_SEARCH_THRESHOLD = h("osk_view_search_threshold", FunctionDescriptor.of(JAVA_INT,
+        ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+    // int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, int32_t n_queries,
+    //     const float* d_min_scores, const uint64_t* const* d_accept, int32_t cap, int32_t* d_docs, float* d_scores,
+    //     int32_t* d_count, int64_t* d_total, int64_t* d_visited, void* stream)
+    static final MethodHandle VIEW_SEARCH_THRESHOLD_DEVICE = h("osk_view_search_threshold_device",
+        FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
+            ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+
     // multi-GPU node (INTEGRATION.md §4)
     static final MethodHandle COMM_UNIQUE_ID = h("osk_comm_unique_id", FunctionDescriptor.of(JAVA_INT, ADDRESS));
     static final MethodHandle COMM_INIT_RANK = h("osk_comm_init_rank", FunctionDescriptor.of(JAVA_INT,
@@ -123,6 +142,46 @@ final class OsKnn {
             return ns.get(JAVA_LONG, 0);
         } catch (Throwable t) {
             return -1;
+        }
+    }
+
+    /** [L] Float/ByteVectorSimilarityQuery over one leaf: every accepted doc of the segment scoring at least
+     *  minScores[q], segment-local docs ascending; outTotal is exact whatever cap (osknn.h). */
+    static void segSearchThreshold(MemorySegment seg, MemorySegment queries, int nQueries, MemorySegment minScores,
+                                   MemorySegment acceptBits, int cap, MemorySegment outDocs, MemorySegment outScores,
+                                   MemorySegment outCount, MemorySegment outTotal, MemorySegment outVisited)
+            throws IOException {
+        try {
+            check((int) SEG_SEARCH_THRESHOLD.invokeExact(seg, queries, nQueries, minScores, acceptBits, cap, outDocs,
+                outScores, outCount, outTotal, outVisited));
+        } catch (Throwable t) {
+            throw wrap(t);
+        }
+    }
+
+    /** The same per shard of a view: outputs [nQueries][nShards][cap], shard-local docs ascending. */
+    static void viewSearchThreshold(MemorySegment view, MemorySegment queries, int nQueries, MemorySegment minScores,
+                                    MemorySegment accept, int cap, MemorySegment outDocs, MemorySegment outScores,
+                                    MemorySegment outCount, MemorySegment outTotal) throws IOException {
+        try {
+            check((int) VIEW_SEARCH_THRESHOLD.invokeExact(view, queries, nQueries, minScores, accept, cap, outDocs,
+                outScores, outCount, outTotal));
+        } catch (Throwable t) {
+            throw wrap(t);
+        }
+    }
+
+    /** The same with device buffers, asynchronous on {@code stream} (NULL = the library's stream). */
+    static void viewSearchThresholdDevice(MemorySegment view, MemorySegment dQueries, int nQueries,
+                                          MemorySegment dMinScores, MemorySegment dAccept, int cap,
+                                          MemorySegment dDocs, MemorySegment dScores, MemorySegment dCount,
+                                          MemorySegment dTotal, MemorySegment dVisited, MemorySegment stream)
+            throws IOException {
+        try {
+            check((int) VIEW_SEARCH_THRESHOLD_DEVICE.invokeExact(view, dQueries, nQueries, dMinScores, dAccept, cap,
+                dDocs, dScores, dCount, dTotal, dVisited, stream));
+        } catch (Throwable t) {
+            throw wrap(t);
         }
     }
 

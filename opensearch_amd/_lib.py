@@ -86,6 +86,9 @@ SIGNATURES = {
     "osk_seg_info": (_I32, [_P, _PI64, _PI32, _PI32, _PI32, _PI32, _PI32]),
     "osk_synth_host": (_I32, [_P, _I64, _I64, _I32, _U64, _I32]),
     "osk_seg_search": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "osk_seg_search_threshold": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "osk_view_search_threshold": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P]),
+    "osk_view_search_threshold_device": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "osk_view_create": (_I32, [_P, _I32, _P, _P, _I32, _P, C.POINTER(_P)]),
     "osk_view_release": (_I32, [_P]),
     "osk_view_search_device": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),

@@ -114,6 +114,13 @@ int32_t check_device(int device) {
     return OSK_OK;
 }
 
+// No device at all: the answer of an entry whose handle cannot be real then (checked before it is read).
+int32_t any_device() {
+    if (device_count_cached() > 0) return OSK_OK;
+    set_error("no HIP device visible (libosknn has no CPU fallback)");
+    return OSK_ERR_NO_DEVICE;
+}
+
 hipStream_t device_stream(int device) {
     std::lock_guard<std::mutex> lk(g_dev_mu);
     if (!g_streams[device]) {
@@ -740,6 +747,7 @@ int32_t osk_view_create(osk_seg* const* segs, int32_t n_segs, const int32_t* seg
     }
     v->shard_tile_begin[n_shards] = (int32_t)tiles.size();
     v->n_tiles = (int)tiles.size();
+    for (const TileDev& td : tiles) v->max_tile_rows = std::max(v->max_tile_rows, td.row_end - td.row_begin);
     // each tile's first row's slot in its shard's candidate region (the select path's collect)
     std::vector<int32_t> tile_coff(std::max<size_t>(1, tiles.size()), 0);
     for (int sh = 0; sh < n_shards; ++sh) {
@@ -2145,6 +2153,70 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
     return OSK_OK;
 }
 
+// Core of osk_view_search_threshold_device (caller holds the view mutex; device already set): passes of up
+// to kThrNQ queries, each one corpus read (thr_scan), a prefix sum (thr_offsets) and an in-order emit.
+int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const float* d_min_scores,
+                              const uint64_t* const* d_accept, int cap, int32_t* d_docs, float* d_scores,
+                              int32_t* d_count, int64_t* d_total, int64_t* d_visited, hipStream_t st) {
+    OSK_REQUIRE(nq >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(cap >= 1, "cap must be >= 1");
+    OSK_REQUIRE(d_queries && d_min_scores && d_docs && d_scores && d_count && d_total, "null device buffer");
+    int32_t rc = order_after_last(v, st);
+    if (rc) return rc;
+    static const int kLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12},
+                                  {32, 8}, {64, 8}, {64, 16}};
+    const int UP = kLV[v->cfg][0] * kLV[v->cfg][1];
+    const int nq_pad = (nq + kThrNQ - 1) / kThrNQ * kThrNQ;
+    const int64_t elem = v->enc == ENC_FLOAT32 ? 4 : 1;
+    const int wpw = thr_words_per_wave(v->cfg, v->max_tile_rows);
+    const size_t waves = (size_t)std::max(1, v->n_tiles) * 4;   // per query of a pass
+    OSK_HIP(v->ws_q.reserve((size_t)nq_pad * UP * 16));
+    OSK_HIP(v->ws_thr_mask.reserve(sizeof(uint64_t) * kThrNQ * waves * wpw));
+    OSK_HIP(v->ws_thr_wcounts.reserve(sizeof(int32_t) * kThrNQ * waves));
+    OSK_HIP(v->ws_thr_offsets.reserve(sizeof(int64_t) * kThrNQ * waves));
+    OSK_HIP(launch_prep_queries(d_queries, (int64_t)v->dim * elem, nq, v->ws_q.p, UP, nq_pad, st));
+    if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
+    v->profile = v->profile_every > 0 && v->profile_tick++ % (uint64_t)v->profile_every == 0;
+    if (v->profile && (rc = profile_begin(v, st, false)) != OSK_OK) return rc;
+
+    ThrParams p{};
+    p.segs = v->d_segs.as<SegDev>();
+    p.tiles = v->d_tiles.as<TileDev>();
+    p.accept = d_accept;
+    p.mask = v->ws_thr_mask.as<uint64_t>();
+    p.counts = v->ws_thr_wcounts.as<int32_t>();
+    p.offsets = v->ws_thr_offsets.as<int64_t>();
+    p.visited = reinterpret_cast<unsigned long long*>(d_visited);
+    p.shard_tile_begin = v->d_shard_tile_begin.as<int32_t>();
+    p.out_docs = d_docs;
+    p.out_scores = d_scores;
+    p.out_count = d_count;
+    p.out_total = d_total;
+    p.n_tiles = v->n_tiles;
+    p.n_shards = v->n_shards;
+    p.wpw = wpw;
+    p.units = v->units;
+    p.sim = v->sim;
+    p.dim = v->dim;
+    p.cap = cap;
+    for (int q0 = 0; q0 < nq; q0 += kThrNQ) {
+        p.q0 = q0;
+        p.q_count = std::min(kThrNQ, nq - q0);
+        p.q = v->ws_q.as<char>() + (size_t)q0 * UP * 16;
+        p.min_score = d_min_scores + q0;
+        if (v->n_tiles > 0) {   // (nothing staged: thr_offsets alone writes zero hits for every shard)
+            OSK_HIP(hipMemsetAsync(p.mask, 0, sizeof(uint64_t) * p.q_count * waves * wpw, st));
+            OSK_HIP(launch_thr_scan(v->enc, v->cfg, p, st, launch_ev_start(v, q0),
+                                    v->profile && q0 + kThrNQ >= nq ? v->ev1 : nullptr));
+        }
+        OSK_HIP(launch_thr_offsets(p, st));
+        if (v->n_tiles > 0) OSK_HIP(launch_thr_emit(v->enc, v->cfg, p, st));
+    }
+    if (v->n_tiles > 0 && (rc = profile_end(v, st, false)) != OSK_OK) return rc;
+    v->thr_calls += 1;
+    return OSK_OK;
+}
+
 }  // namespace osk
 
 extern "C" {
@@ -2161,6 +2233,27 @@ int32_t osk_view_search_device(osk_view* view, const void* d_queries, int32_t n_
     std::lock_guard<std::mutex> lk(view->mu);
     return view_search_device(view, d_queries, n_queries, k, d_accept, d_shard_keys, d_shard_counts,
                               d_visited, st);
+    OSK_GUARD_END
+}
+
+int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, int32_t n_queries,
+                                         const float* d_min_scores, const uint64_t* const* d_accept, int32_t cap,
+                                         int32_t* d_docs, float* d_scores, int32_t* d_count, int64_t* d_total,
+                                         int64_t* d_visited, void* stream) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(view != nullptr, "view is null");
+    OSK_REQUIRE(d_queries && d_min_scores && d_docs && d_scores && d_count && d_total, "null device buffer");
+    OSK_REQUIRE(n_queries >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(cap >= 1, "cap must be >= 1");
+    int32_t rc = any_device();
+    if (rc) return rc;
+    rc = check_device(view->device);
+    if (rc) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(view->device);
+    std::lock_guard<std::mutex> lk(view->mu);
+    return view_threshold_device(view, d_queries, n_queries, d_min_scores, d_accept, cap, d_docs, d_scores, d_count,
+                                 d_total, d_visited, st);
     OSK_GUARD_END
 }
 
@@ -2324,7 +2417,7 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
                      n == "sq8_rows_quarter_end_cycles" || n == "sq8_rows_first_wait_cycles" ||
                      n == "sq8_rows_setup_barrier_cycles" || n == "sq8_rows_setup_fragment_cycles";
     OSK_REQUIRE(dev || n == "mfma_calls" || n == "mfma_fallback_queries" || n == "sq8_calls" || n == "sq6_calls" ||
-                    n == "select_calls" || n == "sq8_wide_calls",
+                    n == "select_calls" || n == "sq8_wide_calls" || n == "threshold_calls",
                 "unknown counter: " + n);
     // summed over the view and the replicas its host entries leased
     int64_t sum = 0;
@@ -2353,7 +2446,7 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
         } else {
             sum += n == "mfma_calls" ? s->mfma_calls : n == "mfma_fallback_queries" ? s->mfma_fallback_queries
                  : n == "sq8_calls" ? s->sq8_calls : n == "sq6_calls" ? s->sq6_calls
-                 : n == "sq8_wide_calls" ? s->sq8w_calls : s->sel_calls;
+                 : n == "sq8_wide_calls" ? s->sq8w_calls : n == "threshold_calls" ? s->thr_calls : s->sel_calls;
         }
     }
     *value = sum;
@@ -2752,6 +2845,131 @@ int32_t osk_seg_search(osk_seg* seg, const void* queries, int32_t n_queries, int
         }
         return OSK_OK;
     });
+    OSK_GUARD_END
+}
+
+// Host-buffer threshold search over a view (synchronous): leases a workspace slot and its stream like
+// view_search_host; never joins the opportunistic batching.  accept: null or n_segs host bitsets;
+// out_visited: null or n_segs.
+static int32_t threshold_host(osk_view* v, const void* queries, int32_t n_queries, const float* min_scores,
+                              const uint64_t* const* accept, int32_t cap, int32_t* out_docs, float* out_scores,
+                              int32_t* out_count, int64_t* out_total, int64_t* out_visited) {
+    ViewLease lease;
+    int32_t rc = lease_view(v, lease);
+    if (rc) return rc;
+    v = lease.v;
+    hipStream_t st = lease.st;
+    std::lock_guard<std::mutex> lk(v->mu);
+    rc = order_after_last(v, st);
+    if (rc) return rc;
+    const int nq = n_queries, S = v->n_shards, ns = (int)v->segs.size();
+    const int64_t elem = v->enc == ENC_FLOAT32 ? 4 : 1;
+    const size_t qbytes = (size_t)nq * v->dim * elem;
+    CallTimer timer;
+    if ((rc = timer.begin(v, st)) != OSK_OK) return rc;
+    const uint64_t* const* d_acc = nullptr;
+    bool any_bits = false;
+    for (int i = 0; accept && i < ns; ++i) any_bits |= accept[i] != nullptr;
+    if (any_bits) {
+        size_t words = 0;
+        for (int i = 0; i < ns; ++i)
+            if (accept[i]) words += (size_t)(v->segs[i]->max_doc + 63) / 64;
+        OSK_HIP(v->ws_accept.reserve(std::max<size_t>(8, words * 8)));
+        OSK_HIP(v->ws_accept_ptrs.reserve(sizeof(void*) * ns));
+        OSK_HIP(v->h_accept_tab.reserve(sizeof(void*) * ns));   // source of an async copy: outlives it
+        const uint64_t** ptrs = static_cast<const uint64_t**>(v->h_accept_tab.p);
+        size_t off = 0;
+        for (int i = 0; i < ns; ++i) {
+            ptrs[i] = nullptr;
+            if (!accept[i]) continue;
+            const size_t w = (size_t)(v->segs[i]->max_doc + 63) / 64;
+            ptrs[i] = v->ws_accept.as<uint64_t>() + off;
+            if (w) OSK_HIP(hipMemcpyAsync(const_cast<uint64_t*>(ptrs[i]), accept[i], w * 8, hipMemcpyHostToDevice, st));
+            off += w;
+        }
+        OSK_HIP(hipMemcpyAsync(v->ws_accept_ptrs.p, ptrs, sizeof(void*) * ns, hipMemcpyHostToDevice, st));
+        d_acc = v->ws_accept_ptrs.as<const uint64_t*>();
+    }
+    OSK_HIP(v->ws_qin.reserve(std::max<size_t>(16, qbytes)));
+    OSK_HIP(hipMemcpyAsync(v->ws_qin.p, queries, qbytes, hipMemcpyHostToDevice, st));
+    OSK_HIP(v->ws_thr_min.reserve(sizeof(float) * nq));
+    OSK_HIP(hipMemcpyAsync(v->ws_thr_min.p, min_scores, sizeof(float) * nq, hipMemcpyHostToDevice, st));
+    // outputs: docs i32 | scores f32 | count i32 | total i64 | visited i64
+    const size_t n_out = (size_t)nq * S * cap, n_qs = (size_t)nq * S;
+    const size_t o_doc = 0, o_sc = o_doc + n_out * 4, o_cnt = o_sc + n_out * 4, o_tot = (o_cnt + n_qs * 4 + 7) / 8 * 8,
+                 o_vis = o_tot + n_qs * 8, total_b = o_vis + (size_t)ns * 8;
+    OSK_HIP(v->ws_thr_out.reserve(total_b));
+    char* ob = v->ws_thr_out.as<char>();
+    rc = view_threshold_device(v, v->ws_qin.p, nq, v->ws_thr_min.as<float>(), d_acc, cap,
+                               reinterpret_cast<int32_t*>(ob + o_doc), reinterpret_cast<float*>(ob + o_sc),
+                               reinterpret_cast<int32_t*>(ob + o_cnt), reinterpret_cast<int64_t*>(ob + o_tot),
+                               reinterpret_cast<int64_t*>(ob + o_vis), st);
+    if (rc) return rc;
+    OSK_HIP(v->h_stage.reserve(total_b));
+    OSK_HIP(hipMemcpyAsync(v->h_stage.p, ob, total_b, hipMemcpyDeviceToHost, st));
+    if ((rc = timer.end()) != OSK_OK) return rc;
+    OSK_HIP(hipStreamSynchronize(st));
+    if ((rc = timer.publish()) != OSK_OK) return rc;
+    const char* hb = static_cast<const char*>(v->h_stage.p);
+    std::memcpy(out_docs, hb + o_doc, n_out * 4);
+    std::memcpy(out_scores, hb + o_sc, n_out * 4);
+    std::memcpy(out_count, hb + o_cnt, n_qs * 4);
+    std::memcpy(out_total, hb + o_tot, n_qs * 8);
+    if (out_visited) std::memcpy(out_visited, hb + o_vis, (size_t)ns * 8);
+    return OSK_OK;
+}
+
+int32_t osk_view_search_threshold(osk_view* view, const void* queries, int32_t n_queries, const float* min_scores,
+                                  const uint64_t* const* accept, int32_t cap, int32_t* out_docs, float* out_scores,
+                                  int32_t* out_count, int64_t* out_total) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(view != nullptr && queries != nullptr && min_scores != nullptr, "null argument");
+    OSK_REQUIRE(out_docs && out_scores && out_count && out_total, "null output");
+    OSK_REQUIRE(n_queries >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(cap >= 1, "cap must be >= 1");
+    int32_t rc = any_device();
+    if (rc) return rc;
+    rc = check_device(view->device);
+    if (rc) return rc;
+    return threshold_host(view, queries, n_queries, min_scores, accept, cap, out_docs, out_scores, out_count,
+                          out_total, nullptr);
+    OSK_GUARD_END
+}
+
+int32_t osk_seg_search_threshold(osk_seg* seg, const void* queries, int32_t n_queries, const float* min_scores,
+                                 const uint64_t* accept_bits, int32_t cap, int32_t* out_docs, float* out_scores,
+                                 int32_t* out_count, int64_t* out_total, int64_t* out_visited) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(seg != nullptr && queries != nullptr && min_scores != nullptr, "null argument");
+    OSK_REQUIRE(out_docs && out_scores && out_count && out_total, "null output");
+    OSK_REQUIRE(n_queries >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(cap >= 1, "cap must be >= 1");
+    int32_t rc = any_device();
+    if (rc) return rc;
+    rc = check_device(seg->device);
+    if (rc) return rc;
+    osk_view* v;
+    {
+        std::lock_guard<std::mutex> lk(seg->mu);
+        if (!seg->self_view) {
+            osk_seg* one[1] = {seg};
+            rc = osk_view_create(one, 1, nullptr, nullptr, 1, nullptr, &seg->self_view);
+            if (rc) return rc;
+            seg->self_view->holds_refs = false;   // owned by the segment: it must not keep the segment alive
+            seg->refs.fetch_sub(1);
+        }
+        v = seg->self_view;
+    }
+    (void)hipSetDevice(seg->device);
+    const uint64_t* acc[1] = {accept_bits};
+    int64_t visited = 0;
+    rc = threshold_host(v, queries, n_queries, min_scores, accept_bits ? acc : nullptr, cap, out_docs, out_scores,
+                        out_count, out_total, &visited);
+    if (rc) return rc;
+    for (int q = 0; out_visited && q < n_queries; ++q) out_visited[q] = visited;
+    return OSK_OK;
     OSK_GUARD_END
 }
 

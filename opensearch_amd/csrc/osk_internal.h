@@ -492,6 +492,44 @@ extern Tuning g_tuning;
 
 hipError_t launch_scan(int enc, int cfg, int nq, const ScanParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
                        hipEvent_t ev_stop = nullptr);
+
+// ---- similarity-threshold search (osk_threshold.hip): every accepted row with score ≥ min_score ----
+// One corpus pass (thr_scan_*: hit mask words + hit counts per (query, tile, wave)), a prefix sum per
+// (query, shard) (thr_offsets: output offsets, totals, counts, unused slots), an in-order emit
+// (thr_emit_*: re-scores the masked rows).  At most kThrNQ queries share a corpus pass.
+constexpr int kThrNQ = 4;
+struct ThrParams {
+    const SegDev* segs;
+    const TileDev* tiles;
+    const uint64_t* const* accept;   // as ScanParams
+    const void* q;                   // this pass's queries, each padded to L*V units (zeros)
+    const float* min_score;          // this pass's thresholds [q_count] (score domain)
+    uint64_t* mask;                  // [kThrNQ][n_tiles][4][wpw] hit bits: wave w of tile t owns wpw words,
+                                     // bit = row − the wave's first row (zeroed before the scan)
+    int32_t* counts;                 // [kThrNQ][n_tiles][4] hits per (query, tile, wave)
+    int64_t* offsets;                // [kThrNQ][n_tiles][4] their exclusive prefix sum within the shard
+    unsigned long long* visited;     // [n_segs] or null (counted by the q0 == 0 pass only)
+    const int32_t* shard_tile_begin; // [n_shards + 1]
+    int32_t* out_docs;               // [n_queries][n_shards][cap] shard-local docs ascending (INT32_MAX past count)
+    float* out_scores;               // [n_queries][n_shards][cap] (−inf past count)
+    int32_t* out_count;              // [n_queries][n_shards] min(total, cap)
+    int64_t* out_total;              // [n_queries][n_shards] exact number of hits
+    int n_tiles;
+    int n_shards;
+    int wpw;                         // mask words per wave (thr_words_per_wave of the view's largest tile)
+    int q0;                          // global index of this pass's first query
+    int q_count;                     // queries in this pass (≤ kThrNQ)
+    int units;
+    int sim;
+    int dim;
+    int cap;
+};
+int thr_words_per_wave(int cfg, int64_t max_tile_rows);
+// Every launcher checks its grid, LDS and arguments and returns hipErrorInvalidValue instead of launching.
+hipError_t launch_thr_scan(int enc, int cfg, const ThrParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
+                           hipEvent_t ev_stop = nullptr);
+hipError_t launch_thr_offsets(const ThrParams& p, hipStream_t s);
+hipError_t launch_thr_emit(int enc, int cfg, const ThrParams& p, hipStream_t s);
 hipError_t launch_row_norms_f32(const float4* rows, int64_t n_rows, int units, int cfg,
                                 float* out, hipStream_t s);
 hipError_t launch_row_norms_i8(const int4* rows, int64_t n_rows, int units, int32_t* out,

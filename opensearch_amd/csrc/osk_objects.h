@@ -223,6 +223,11 @@ struct osk_view {
     // the select path (osk_select.hip, any k): per-row records of one query, radix state, candidates
     osk::DevBuf ws_sel_lb, ws_sel_ub, ws_sel_keys, ws_sel_state, ws_sel_hist, ws_sel_cand, ws_sel_cand2, ws_sel_cnt;
     int64_t sel_calls = 0;
+    // similarity-threshold search (osk_threshold.hip): hit mask, per-wave counts and offsets of one corpus
+    // pass (≤ kThrNQ queries), the thresholds, and the host entries' device outputs
+    int64_t max_tile_rows = 0;             // the largest tile's rows (sizes the mask: thr_words_per_wave)
+    osk::DevBuf ws_thr_mask, ws_thr_wcounts, ws_thr_offsets, ws_thr_min, ws_thr_out;
+    int64_t thr_calls = 0;
     bool gather_ready = false;
     int n_gtiles = 0, n_gslices = 0;
     osk::DevBuf d_gtiles, d_gslices, d_gshard_slice_begin, d_seg_tiles;
@@ -292,4 +297,8 @@ int32_t lease_view(osk_view* root, ViewLease& out);
 // Per-shard exact top-k on the device (caller holds v->mu; device current).
 int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k, const uint64_t* const* d_accept,
                            uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st);
+// Per-shard similarity-threshold search on the device (caller holds v->mu; device current).
+int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const float* d_min_scores,
+                              const uint64_t* const* d_accept, int cap, int32_t* d_docs, float* d_scores,
+                              int32_t* d_count, int64_t* d_total, int64_t* d_visited, hipStream_t st);
 }  // namespace osk

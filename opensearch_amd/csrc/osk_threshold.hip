@@ -1,0 +1,585 @@
+// osk_threshold.hip — exact similarity-threshold (radial) search: every accepted row whose score is
+// ≥ min_score, in ascending doc order, with an exact count ([L] AbstractVectorSimilarityQuery /
+// FloatVectorSimilarityQuery / ByteVectorSimilarityQuery over a flat field; OpenSearch's k-NN
+// `min_score`).  DESIGN.md §3h.
+//
+//   thr_scan_f32 / thr_scan_i8   the only pass that reads the corpus: scan_f32 / scan_i8's tiles, lane
+//                                layout, filter pushdown and score arithmetic, with the wave top-k list
+//                                replaced by `hit = valid && score >= min_score` → one ballot per row
+//                                group → 64-bit mask words + a per-(query, tile, wave) hit count.
+//                                No score round-trips through HBM.
+//   thr_offsets                  per (query, shard): exclusive prefix sum of the wave counts in tile
+//                                order (= segment by doc_base, then row, order) → each wave's output
+//                                offset, the shard's exact total, min(total, cap), and the unused
+//                                output slots' sentinels.
+//   thr_emit_f32 / thr_emit_i8   per (query, tile, wave): walk the mask words and re-score each set bit's
+//                                row with the same function (L lanes per row); doc + score go to
+//                                offset + rank when that is < cap.  The hit decision is the mask's.
+//
+// Mask word ownership: a wave's row range is a multiple of R = 64/L rows, not of 64, and under a filter
+// on a dense field the walk visits compacted rows — so every wave owns `wpw` words of its own
+// (bit = row − the wave's first row) and no two waves ever store the same word.  The mask is zeroed
+// by the host before the scan; a wave stores only its non-zero words (plain vector stores).
+#include <hip/hip_ext.h>
+
+#include <algorithm>
+
+#include "osk_device.h"
+#include "osk_internal.h"
+#include "osk_wave.h"
+
+namespace osk {
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// the shared per-row arithmetic (scan_f32 / scan_i8's, operation for operation): both the scan and the
+// emit call these, so a row's score has the same bits in both — and the bits of the k-NN scans
+// ------------------------------------------------------------------------------------------------
+template <bool NT>
+__device__ __forceinline__ float4 thr_load4(const float4* p) {
+    if constexpr (NT) {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
+        return make_float4(v.x, v.y, v.z, v.w);
+    } else {
+        return *p;
+    }
+}
+
+template <int L, int V, bool NT>
+__device__ __forceinline__ void thr_load_row_f32(const float4* xr, bool valid, int units, int t, float4 (&xv)[V]) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const int f = t + j * L;
+        xv[j] = (valid && f < units) ? thr_load4<NT>(xr + f) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// |q|² in the row norms' lane layout (COSINE)
+template <int L, int V, class QAt>
+__device__ __forceinline__ float thr_qnorm_f32(QAt&& qat) {
+    float ax = 0.f, ay = 0.f, az = 0.f, aw = 0.f;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const float4 qv = qat(j);
+        ax = fmaf(qv.x, qv.x, ax); ay = fmaf(qv.y, qv.y, ay);
+        az = fmaf(qv.z, qv.z, az); aw = fmaf(qv.w, qv.w, aw);
+    }
+    float s = (ax + ay) + (az + aw);
+    return lane_sum<L>(s);
+}
+
+template <int L, int V, bool L2K, class QAt>
+__device__ __forceinline__ float thr_score_f32(const float4 (&xv)[V], QAt&& qat, int sim, float qn, float xn) {
+    float ax = 0.f, ay = 0.f, az = 0.f, aw = 0.f;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const float4 qv = qat(j);
+        if constexpr (L2K) {
+            const float dx = xv[j].x - qv.x, dy = xv[j].y - qv.y;
+            const float dz = xv[j].z - qv.z, dw = xv[j].w - qv.w;
+            ax = fmaf(dx, dx, ax); ay = fmaf(dy, dy, ay);
+            az = fmaf(dz, dz, az); aw = fmaf(dw, dw, aw);
+        } else {
+            ax = fmaf(xv[j].x, qv.x, ax); ay = fmaf(xv[j].y, qv.y, ay);
+            az = fmaf(xv[j].z, qv.z, az); aw = fmaf(xv[j].w, qv.w, aw);
+        }
+    }
+    float s = (ax + ay) + (az + aw);
+    s = lane_sum<L>(s);
+    if constexpr (L2K) return score_f32_l2(s);
+    else return score_f32(sim, s, qn, xn);
+}
+
+__device__ __forceinline__ int thr_dot4(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
+
+template <int L, int V>
+__device__ __forceinline__ void thr_load_row_i8(const int4* xr, bool valid, int units, int t, int4 (&xv)[V]) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const int f = t + j * L;
+        xv[j] = (valid && f < units) ? xr[f] : make_int4(0, 0, 0, 0);
+    }
+}
+
+template <int L, int V, class QAt>
+__device__ __forceinline__ int32_t thr_qnorm_i8(QAt&& qat) {   // Σq² (exact)
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const int4 qv = qat(j);
+        acc = thr_dot4(qv.x, qv.x, acc); acc = thr_dot4(qv.y, qv.y, acc);
+        acc = thr_dot4(qv.z, qv.z, acc); acc = thr_dot4(qv.w, qv.w, acc);
+    }
+    return lane_sum<L>(acc);
+}
+
+template <int L, int V, class QAt>
+__device__ __forceinline__ float thr_score_i8(const int4 (&xv)[V], QAt&& qat, int sim, int32_t qn, int32_t xn, int dim) {
+    int acc = 0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const int4 qv = qat(j);
+        acc = thr_dot4(xv[j].x, qv.x, acc);
+        acc = thr_dot4(xv[j].y, qv.y, acc);
+        acc = thr_dot4(xv[j].z, qv.z, acc);
+        acc = thr_dot4(xv[j].w, qv.w, acc);
+    }
+    acc = lane_sum<L>(acc);
+    const int32_t s = sim == SIM_EUCLIDEAN ? qn + xn - 2 * acc : acc;
+    return score_i8(sim, s, qn, xn, dim);
+}
+
+// A wave's rows of a tile (the k-NN scans' split: 4 waves, each a multiple of R rows)
+template <int R>
+__device__ __forceinline__ void thr_wave_range(const TileDev& tile, int wave, int64_t& wb, int64_t& we) {
+    const int64_t rows = tile.row_end - tile.row_begin;
+    const int64_t per_wave = ((rows + 4 * R - 1) / (4 * R)) * R;
+    wb = min(tile.row_begin + wave * per_wave, tile.row_end);
+    we = min(wb + per_wave, tile.row_end);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The hit mask of a wave for NQ queries: the word in progress per query (wave-uniform), flushed when
+// the walk moves to another word.  Every row group of one walk step lies inside ONE word: unfiltered
+// steps are R | 64 consecutive rows starting at a multiple of R from the wave's first row; compacted
+// steps (walk_rows under a filter on a dense field) take their rows from one 64-row window that starts
+// at a multiple of 64 from it.
+// ------------------------------------------------------------------------------------------------
+template <int NQ>
+struct ThrMask {
+    uint64_t bits[NQ];
+    uint32_t cnt[NQ];
+    int idx;
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int b = 0; b < NQ; ++b) { bits[b] = 0ull; cnt[b] = 0u; }
+        idx = 0;
+    }
+    // mw: this wave's words of query 0; query b's are at mw + b·qstride
+    __device__ __forceinline__ void flush(uint64_t* mw, size_t qstride, int wpw, int q_count, int lane) {
+#pragma unroll
+        for (int b = 0; b < NQ; ++b) {
+            if (bits[b] != 0ull && b < q_count && idx < wpw) {
+                if (lane == 0) mw[b * qstride + idx] = bits[b];
+                cnt[b] += (uint32_t)__popcll(bits[b]);
+            }
+            bits[b] = 0ull;
+        }
+    }
+};
+
+// One walk step's hits of query b → bits of the step's word.  `hit` is the same in all L lanes of a
+// row group.  contiguous: group g is bit (rel0 & 63) + g; else each hit row sets its own bit.
+template <int L>
+__device__ __forceinline__ uint64_t thr_step_bits(bool hit, bool contiguous, int rel, int lane, int t) {
+    constexpr int R = 64 / L;
+    if (contiguous) {
+        const int hg = __shfl((int)hit, (lane & (R - 1)) * L);
+        const uint64_t m = __ballot(hg != 0 && lane < R);
+        const int rel0 = __builtin_amdgcn_readfirstlane(rel);   // lane 0 = group 0 = the step's first row
+        return m << (rel0 & 63);
+    }
+    uint64_t out = 0ull;
+    uint64_t hm = __ballot(t == 0 && hit);
+    while (hm) {
+        const int src = __builtin_ctzll(hm);
+        const int r = __builtin_amdgcn_readlane(rel, src);
+        out |= 1ull << (r & 63);
+        hm &= hm - 1ull;
+    }
+    return out;
+}
+
+// ------------------------------------------------------------------------------------------------
+// scan, float32
+// ------------------------------------------------------------------------------------------------
+template <int L, int V, int NQ, bool L2K, bool NT>
+__global__ __launch_bounds__(kBlock) void thr_scan_f32(ThrParams p) {
+    constexpr int R = 64 / L;
+    constexpr int UP = L * V;
+    constexpr bool QREG = NQ * V * 4 <= 64;   // query fragments in VGPRs, else read from LDS (scan_f32's rule)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float4* sq = reinterpret_cast<float4*>(smem);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t = lane & (L - 1), g = lane / L;
+    const TileDev tile = p.tiles[blockIdx.x];
+    const SegDev seg = p.segs[tile.seg];
+    const float4* __restrict__ X = static_cast<const float4*>(seg.rows);
+    const float4* __restrict__ Q = static_cast<const float4*>(p.q);
+    const int units = p.units;
+
+    float4 qf[QREG ? NQ : 1][QREG ? V : 1];
+    if constexpr (QREG) {
+#pragma unroll
+        for (int b = 0; b < NQ; ++b)
+#pragma unroll
+            for (int j = 0; j < V; ++j) qf[b][j] = Q[b * UP + t + j * L];
+    } else {
+        for (int i = tid; i < NQ * UP; i += kBlock) sq[i] = Q[i];
+        __syncthreads();
+    }
+    auto qat = [&](int b, int j) -> float4 {
+        if constexpr (QREG) return qf[b][j];
+        else return sq[b * UP + t + j * L];
+    };
+    const int sim = p.sim;
+    float qn[NQ], ms[NQ];
+#pragma unroll
+    for (int b = 0; b < NQ; ++b) {
+        qn[b] = 0.0f;
+        if (!L2K && sim == SIM_COSINE) qn[b] = thr_qnorm_f32<L, V>([&](int j) { return qat(b, j); });
+        ms[b] = b < p.q_count ? p.min_score[b] : __builtin_nanf("");
+    }
+
+    int64_t wb, we;
+    thr_wave_range<R>(tile, wave, wb, we);
+    const uint64_t* abits = p.accept ? p.accept[tile.seg] : nullptr;
+    const size_t qstride = (size_t)p.n_tiles * 4 * p.wpw;
+    const size_t wi = (size_t)blockIdx.x * 4 + wave;
+    uint64_t* mw = p.mask + wi * p.wpw;
+
+    ThrMask<NQ> hm;
+    hm.init();
+    uint32_t nvis = 0;
+
+    walk_rows<R>(wb, we, abits, seg.ord_to_doc, lane, g, [&](const int64_t row, bool valid, bool accepted_known) {
+        int32_t doc = 0;
+        if (valid) {
+            doc = seg.ord_to_doc ? seg.ord_to_doc[row] : (int32_t)row;
+            if (abits && !accepted_known) valid = (abits[doc >> 6] >> (doc & 63)) & 1ull;
+        }
+        float4 xv[V];
+        thr_load_row_f32<L, V, NT>(X + row * units, valid, units, t, xv);
+        float xn = 0.0f;
+        if (!L2K && sim == SIM_COSINE && valid) xn = seg.xnorm_f[row];
+        nvis += __popcll(__ballot(t == 0 && valid));
+
+        const int rel = (int)(row - wb);
+        const int widx = __builtin_amdgcn_readfirstlane(rel) >> 6;
+        if (widx != hm.idx) {
+            hm.flush(mw, qstride, p.wpw, p.q_count, lane);
+            hm.idx = widx;
+        }
+#pragma unroll
+        for (int b = 0; b < NQ; ++b) {
+            const float sc = thr_score_f32<L, V, L2K>(xv, [&](int j) { return qat(b, j); }, sim, qn[b], xn);
+            const bool hit = valid && sc >= ms[b];   // IEEE compare: NaN on either side is no hit, −0 == +0
+            hm.bits[b] |= thr_step_bits<L>(hit, !accepted_known, rel, lane, t);
+        }
+    });
+    hm.flush(mw, qstride, p.wpw, p.q_count, lane);
+
+    if (lane == 0) {
+#pragma unroll
+        for (int b = 0; b < NQ; ++b)
+            if (b < p.q_count) p.counts[(size_t)b * p.n_tiles * 4 + wi] = (int32_t)hm.cnt[b];
+    }
+    if (p.visited && p.q0 == 0) add_visited_wg(&p.visited[tile.seg], nvis);
+}
+
+// ------------------------------------------------------------------------------------------------
+// scan, int8 (exact int32 sums)
+// ------------------------------------------------------------------------------------------------
+template <int L, int V, int NQ>
+__global__ __launch_bounds__(kBlock) void thr_scan_i8(ThrParams p) {
+    constexpr int R = 64 / L;
+    constexpr int UP = L * V;
+    constexpr bool QREG = NQ * V * 4 <= 64;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int4* sq = reinterpret_cast<int4*>(smem);
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t = lane & (L - 1), g = lane / L;
+    const TileDev tile = p.tiles[blockIdx.x];
+    const SegDev seg = p.segs[tile.seg];
+    const int4* __restrict__ X = static_cast<const int4*>(seg.rows);
+    const int4* __restrict__ Q = static_cast<const int4*>(p.q);
+    const int units = p.units;
+
+    int4 qf[QREG ? NQ : 1][QREG ? V : 1];
+    if constexpr (QREG) {
+#pragma unroll
+        for (int b = 0; b < NQ; ++b)
+#pragma unroll
+            for (int j = 0; j < V; ++j) qf[b][j] = Q[b * UP + t + j * L];
+    } else {
+        for (int i = tid; i < NQ * UP; i += kBlock) sq[i] = Q[i];
+        __syncthreads();
+    }
+    auto qat = [&](int b, int j) -> int4 {
+        if constexpr (QREG) return qf[b][j];
+        else return sq[b * UP + t + j * L];
+    };
+    const int sim = p.sim, dim = p.dim;
+    int32_t qn[NQ];
+    float ms[NQ];
+#pragma unroll
+    for (int b = 0; b < NQ; ++b) {
+        qn[b] = thr_qnorm_i8<L, V>([&](int j) { return qat(b, j); });
+        ms[b] = b < p.q_count ? p.min_score[b] : __builtin_nanf("");
+    }
+
+    int64_t wb, we;
+    thr_wave_range<R>(tile, wave, wb, we);
+    const uint64_t* abits = p.accept ? p.accept[tile.seg] : nullptr;
+    const size_t qstride = (size_t)p.n_tiles * 4 * p.wpw;
+    const size_t wi = (size_t)blockIdx.x * 4 + wave;
+    uint64_t* mw = p.mask + wi * p.wpw;
+
+    ThrMask<NQ> hm;
+    hm.init();
+    uint32_t nvis = 0;
+
+    walk_rows<R>(wb, we, abits, seg.ord_to_doc, lane, g, [&](const int64_t row, bool valid, bool accepted_known) {
+        int32_t doc = 0;
+        if (valid) {
+            doc = seg.ord_to_doc ? seg.ord_to_doc[row] : (int32_t)row;
+            if (abits && !accepted_known) valid = (abits[doc >> 6] >> (doc & 63)) & 1ull;
+        }
+        int4 xv[V];
+        thr_load_row_i8<L, V>(X + row * units, valid, units, t, xv);
+        const int32_t xn = valid ? seg.xnorm_i[row] : 0;
+        nvis += __popcll(__ballot(t == 0 && valid));
+
+        const int rel = (int)(row - wb);
+        const int widx = __builtin_amdgcn_readfirstlane(rel) >> 6;
+        if (widx != hm.idx) {
+            hm.flush(mw, qstride, p.wpw, p.q_count, lane);
+            hm.idx = widx;
+        }
+#pragma unroll
+        for (int b = 0; b < NQ; ++b) {
+            const float sc = thr_score_i8<L, V>(xv, [&](int j) { return qat(b, j); }, sim, qn[b], xn, dim);
+            const bool hit = valid && sc >= ms[b];
+            hm.bits[b] |= thr_step_bits<L>(hit, !accepted_known, rel, lane, t);
+        }
+    });
+    hm.flush(mw, qstride, p.wpw, p.q_count, lane);
+
+    if (lane == 0) {
+#pragma unroll
+        for (int b = 0; b < NQ; ++b)
+            if (b < p.q_count) p.counts[(size_t)b * p.n_tiles * 4 + wi] = (int32_t)hm.cnt[b];
+    }
+    if (p.visited && p.q0 == 0) add_visited_wg(&p.visited[tile.seg], nvis);
+}
+
+// ------------------------------------------------------------------------------------------------
+// offsets: one workgroup per (shard, query of the pass)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void thr_offsets(ThrParams p) {
+    __shared__ long long s_wave[kBlock / 64];
+    const int s = blockIdx.x, b = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t0 = p.shard_tile_begin[s], t1 = p.shard_tile_begin[s + 1];
+    const int64_t n = (int64_t)(t1 - t0) * 4;
+    const size_t base = ((size_t)b * p.n_tiles + t0) * 4;
+    long long carry = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += kBlock) {
+        const int64_t i = i0 + tid;
+        const long long v = i < n ? (long long)p.counts[base + i] : 0ll;
+        long long x = v;   // inclusive scan over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const long long y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63) s_wave[wave] = x;
+        __syncthreads();
+        long long pre = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) {
+            if (w < wave) pre += s_wave[w];
+            all += s_wave[w];
+        }
+        if (i < n) p.offsets[base + i] = carry + pre + x - v;
+        carry += all;
+        __syncthreads();
+    }
+    const size_t o = (size_t)(p.q0 + b) * p.n_shards + s;
+    const long long cnt = carry < (long long)p.cap ? carry : (long long)p.cap;
+    if (tid == 0) {
+        p.out_total[o] = carry;
+        p.out_count[o] = (int32_t)cnt;
+    }
+    // unused slots, as osk_seg_search leaves them
+    for (int64_t i = cnt + tid; i < p.cap; i += kBlock) {
+        p.out_docs[o * p.cap + i] = 0x7FFFFFFF;
+        p.out_scores[o * p.cap + i] = -__builtin_inff();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// emit: one workgroup per (tile, query of the pass); each wave re-scores its own mask's rows
+// ------------------------------------------------------------------------------------------------
+template <int L, int V, bool L2K>
+__global__ __launch_bounds__(kBlock) void thr_emit_f32(ThrParams p) {
+    constexpr int R = 64 / L;
+    constexpr int UP = L * V;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t = lane & (L - 1), g = lane / L;
+    const int b = blockIdx.y;
+    const size_t wi = ((size_t)b * p.n_tiles + blockIdx.x) * 4 + wave;
+    if (p.counts[wi] == 0) return;
+    int64_t rank = p.offsets[wi];
+    if (rank >= p.cap) return;   // past the capacity: counted, not returned
+    const TileDev tile = p.tiles[blockIdx.x];
+    const SegDev seg = p.segs[tile.seg];
+    const float4* __restrict__ X = static_cast<const float4*>(seg.rows);
+    const float4* __restrict__ Q = static_cast<const float4*>(p.q) + (size_t)b * UP;
+    const int units = p.units, sim = p.sim;
+    float4 qf[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) qf[j] = Q[t + j * L];
+    auto qat = [&](int j) -> float4 { return qf[j]; };
+    float qn = 0.0f;
+    if (!L2K && sim == SIM_COSINE) qn = thr_qnorm_f32<L, V>(qat);
+    int64_t wb, we;
+    thr_wave_range<R>(tile, wave, wb, we);
+    const size_t o = ((size_t)(p.q0 + b) * p.n_shards + tile.shard) * (size_t)p.cap;
+    // the wave's mask words are a bitset over its rows relative to wb: walk_rows' compaction visits
+    // exactly the set bits, in ascending order, R per step
+    walk_rows<R>(0, we - wb, p.mask + wi * p.wpw, nullptr, lane, g, [&](const int64_t rel, bool valid, bool) {
+        const int64_t row = wb + rel;
+        float4 xv[V];
+        thr_load_row_f32<L, V, false>(X + row * units, valid, units, t, xv);
+        float xn = 0.0f;
+        if (!L2K && sim == SIM_COSINE && valid) xn = seg.xnorm_f[row];
+        const float sc = thr_score_f32<L, V, L2K>(xv, qat, sim, qn, xn);
+        const uint64_t vm = __ballot(t == 0 && valid);
+        const int64_t pos = rank + __popcll(vm & ((1ull << lane) - 1ull));
+        if (t == 0 && valid && pos < p.cap) {
+            const int32_t doc = seg.ord_to_doc ? seg.ord_to_doc[row] : (int32_t)row;
+            p.out_docs[o + pos] = seg.doc_base + doc;
+            p.out_scores[o + pos] = sc;
+        }
+        rank += __popcll(vm);
+    });
+}
+
+template <int L, int V>
+__global__ __launch_bounds__(kBlock) void thr_emit_i8(ThrParams p) {
+    constexpr int R = 64 / L;
+    constexpr int UP = L * V;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t = lane & (L - 1), g = lane / L;
+    const int b = blockIdx.y;
+    const size_t wi = ((size_t)b * p.n_tiles + blockIdx.x) * 4 + wave;
+    if (p.counts[wi] == 0) return;
+    int64_t rank = p.offsets[wi];
+    if (rank >= p.cap) return;
+    const TileDev tile = p.tiles[blockIdx.x];
+    const SegDev seg = p.segs[tile.seg];
+    const int4* __restrict__ X = static_cast<const int4*>(seg.rows);
+    const int4* __restrict__ Q = static_cast<const int4*>(p.q) + (size_t)b * UP;
+    const int units = p.units, sim = p.sim, dim = p.dim;
+    int4 qf[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) qf[j] = Q[t + j * L];
+    auto qat = [&](int j) -> int4 { return qf[j]; };
+    const int32_t qn = thr_qnorm_i8<L, V>(qat);
+    int64_t wb, we;
+    thr_wave_range<R>(tile, wave, wb, we);
+    const size_t o = ((size_t)(p.q0 + b) * p.n_shards + tile.shard) * (size_t)p.cap;
+    walk_rows<R>(0, we - wb, p.mask + wi * p.wpw, nullptr, lane, g, [&](const int64_t rel, bool valid, bool) {
+        const int64_t row = wb + rel;
+        int4 xv[V];
+        thr_load_row_i8<L, V>(X + row * units, valid, units, t, xv);
+        const int32_t xn = valid ? seg.xnorm_i[row] : 0;
+        const float sc = thr_score_i8<L, V>(xv, qat, sim, qn, xn, dim);
+        const uint64_t vm = __ballot(t == 0 && valid);
+        const int64_t pos = rank + __popcll(vm & ((1ull << lane) - 1ull));
+        if (t == 0 && valid && pos < p.cap) {
+            const int32_t doc = seg.ord_to_doc ? seg.ord_to_doc[row] : (int32_t)row;
+            p.out_docs[o + pos] = seg.doc_base + doc;
+            p.out_scores[o + pos] = sc;
+        }
+        rank += __popcll(vm);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// dispatch: the scans' lane configs × NQ ∈ {1, kThrNQ} × {L2, dot-family} × {plain, non-temporal}
+// ------------------------------------------------------------------------------------------------
+using ThrFn = void (*)(ThrParams);
+constexpr int kLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12}, {32, 8}, {64, 8}, {64, 16}};
+constexpr size_t kLdsMax = 160 * 1024;   // LDS per workgroup on gfx950
+
+#define OSK_THR_F32_NT(L, V, NT)                                                                        \
+    thr_scan_f32<L, V, 1, true, NT>, thr_scan_f32<L, V, kThrNQ, true, NT>, thr_scan_f32<L, V, 1, false, NT>, \
+        thr_scan_f32<L, V, kThrNQ, false, NT>
+#define OSK_THR_F32(L, V) {OSK_THR_F32_NT(L, V, false), OSK_THR_F32_NT(L, V, true)}
+#define OSK_THR_I8(L, V) {thr_scan_i8<L, V, 1>, thr_scan_i8<L, V, kThrNQ>}
+#define OSK_THR_EMIT(L, V) {thr_emit_f32<L, V, true>, thr_emit_f32<L, V, false>}
+
+const ThrFn kThrScanF32[9][8] = {OSK_THR_F32(4, 2),  OSK_THR_F32(8, 2),   OSK_THR_F32(8, 4),
+                                 OSK_THR_F32(16, 4), OSK_THR_F32(16, 8),  OSK_THR_F32(16, 12),
+                                 OSK_THR_F32(32, 8), OSK_THR_F32(64, 8),  OSK_THR_F32(64, 16)};
+const ThrFn kThrScanI8[9][2] = {OSK_THR_I8(4, 2),  OSK_THR_I8(8, 2),  OSK_THR_I8(8, 4),
+                                OSK_THR_I8(16, 4), OSK_THR_I8(16, 8), OSK_THR_I8(16, 12),
+                                OSK_THR_I8(32, 8), OSK_THR_I8(64, 8), OSK_THR_I8(64, 16)};
+const ThrFn kThrEmitF32[9][2] = {OSK_THR_EMIT(4, 2),  OSK_THR_EMIT(8, 2),  OSK_THR_EMIT(8, 4),
+                                 OSK_THR_EMIT(16, 4), OSK_THR_EMIT(16, 8), OSK_THR_EMIT(16, 12),
+                                 OSK_THR_EMIT(32, 8), OSK_THR_EMIT(64, 8), OSK_THR_EMIT(64, 16)};
+const ThrFn kThrEmitI8[9] = {thr_emit_i8<4, 2>,  thr_emit_i8<8, 2>,  thr_emit_i8<8, 4>,
+                             thr_emit_i8<16, 4>, thr_emit_i8<16, 8>, thr_emit_i8<16, 12>,
+                             thr_emit_i8<32, 8>, thr_emit_i8<64, 8>, thr_emit_i8<64, 16>};
+
+// what every launch of a pass must satisfy; anything else is refused, never guessed
+bool thr_params_ok(int enc, int cfg, const ThrParams& p) {
+    return (enc == ENC_FLOAT32 || enc == ENC_BYTE) && cfg >= 0 && cfg < 9 && p.sim >= 0 && p.sim <= 3 &&
+           p.q_count >= 1 && p.q_count <= kThrNQ && p.n_shards >= 1 && p.cap >= 1 &&
+           p.wpw >= 1 && p.n_tiles >= 0 && p.units >= 1 && p.units <= kLV[cfg][0] * kLV[cfg][1] &&
+           p.segs && p.tiles && p.q && p.min_score && p.mask && p.counts && p.offsets && p.shard_tile_begin &&
+           p.out_docs && p.out_scores && p.out_count && p.out_total;
+}
+
+}  // namespace
+
+int thr_words_per_wave(int cfg, int64_t max_tile_rows) {
+    if (cfg < 0 || cfg >= 9 || max_tile_rows < 1) return 1;
+    const int64_t R = 64 / kLV[cfg][0];
+    const int64_t per_wave = ((max_tile_rows + 4 * R - 1) / (4 * R)) * R;
+    return (int)std::min<int64_t>(0x7FFFFFFF, (per_wave + 63) / 64);
+}
+
+hipError_t launch_thr_scan(int enc, int cfg, const ThrParams& p, hipStream_t s, hipEvent_t ev_start,
+                           hipEvent_t ev_stop) {
+    if (!thr_params_ok(enc, cfg, p) || p.n_tiles < 1) return hipErrorInvalidValue;
+    const int slot = p.q_count <= 1 ? 0 : 1;
+    const int NQ = slot ? kThrNQ : 1;
+    const int L = kLV[cfg][0], V = kLV[cfg][1];
+    const bool qreg = NQ * V * 4 <= 64;
+    const size_t lds = qreg ? 0 : (size_t)NQ * L * V * 16;
+    if (lds > kLdsMax) return hipErrorInvalidValue;
+    ThrFn fn;
+    if (enc == ENC_FLOAT32)
+        fn = kThrScanF32[cfg][(g_tuning.scan_nt ? 4 : 0) + (p.sim == SIM_EUCLIDEAN ? 0 : 2) + slot];
+    else
+        fn = kThrScanI8[cfg][slot];
+    if (ev_start || ev_stop)
+        hipExtLaunchKernelGGL(fn, dim3(p.n_tiles), dim3(kBlock), lds, s, ev_start, ev_stop, 0, p);
+    else
+        hipLaunchKernelGGL(fn, dim3(p.n_tiles), dim3(kBlock), lds, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_thr_offsets(const ThrParams& p, hipStream_t s) {
+    if (p.q_count < 1 || p.q_count > kThrNQ || p.n_shards < 1 || p.cap < 1 || p.n_tiles < 0 || !p.counts ||
+        !p.offsets || !p.shard_tile_begin || !p.out_docs || !p.out_scores || !p.out_count || !p.out_total)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(thr_offsets, dim3(p.n_shards, p.q_count), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_thr_emit(int enc, int cfg, const ThrParams& p, hipStream_t s) {
+    if (!thr_params_ok(enc, cfg, p) || p.n_tiles < 1) return hipErrorInvalidValue;
+    const ThrFn fn = enc == ENC_FLOAT32 ? kThrEmitF32[cfg][p.sim == SIM_EUCLIDEAN ? 0 : 1] : kThrEmitI8[cfg];
+    hipLaunchKernelGGL(fn, dim3(p.n_tiles, p.q_count), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace osk

@@ -11,10 +11,13 @@ plugin's public request format so existing requests keep working:
             "space_type": "l2" | "innerproduct" | "cosinesimil" | "dot_product",
             "method": {"name": "flat", "engine": "gpu"}}                     (method optional)
   query    {"knn": {"<field>": {"vector": [...], "k": 10, "filter": <query>}}}
+           {"knn": {"<field>": {"vector": [...], "min_score": 0.8, "filter": <query>}}}   (radial search:
+           every document scoring at least min_score; exactly one of k / min_score)
 
 `KnnQueryBuilder.do_to_query` ([L] AbstractQueryBuilder.doToQuery, S/index/query/AbstractQueryBuilder.java:
 155) returns Lucene's own `KnnFloatVectorQuery` / `KnnByteVectorQuery` (opensearch_amd.lucene), whose
-per-leaf search runs on the GPU reader.  The filter is any query over the shard's doc values that
+per-leaf search runs on the GPU reader — or, for `min_score`, [L] `FloatVectorSimilarityQuery` /
+`ByteVectorSimilarityQuery` with resultSimilarity = min_score.  The filter is any query over the shard's doc values that
 this module parses (term / terms / range / bool / match_all), evaluated per leaf into the accept mask
 ([L] the filter Weight → AcceptDocs; OpenSearch caches such bitsets in BitsetFilterCache,
 S/index/cache/bitset/BitsetFilterCache.java:127-160).  Contract tests mirror AbstractQueryTestCase
@@ -23,13 +26,15 @@ S/index/cache/bitset/BitsetFilterCache.java:127-160).  Contract tests mirror Abs
 from __future__ import annotations
 
 import json
+import math
 import struct
 from dataclasses import dataclass, field
 from typing import Any, Callable
 
 import numpy as np
 
-from .lucene import KnnByteVectorQuery, KnnFloatVectorQuery, VectorEncoding, VectorSimilarityFunction
+from .lucene import (ByteVectorSimilarityQuery, FloatVectorSimilarityQuery, KnnByteVectorQuery, KnnFloatVectorQuery,
+                     VectorEncoding, VectorSimilarityFunction)
 
 MAX_RESULT_WINDOW = 10000          # index.max_result_window default, S/index/IndexSettings.java:223-226
 MAX_DIMENSION = 4096               # libosknn's OSK_MAX_DIM
@@ -191,18 +196,27 @@ class KnnQueryBuilder:
     """[L]-backed `knn` QueryBuilder (S/index/query/AbstractQueryBuilder.java:69)."""
     field_name: str
     vector: list
-    k: int
+    k: int | None = None
     filter: dict | None = None
     boost: float = 1.0
     query_name: str | None = None
+    min_score: float | None = None    # radial search: every doc scoring ≥ min_score (in place of k)
 
     def __post_init__(self):
         if not self.field_name:
             raise ValueError("[knn] requires a field name")
-        if not isinstance(self.k, int) or isinstance(self.k, bool) or self.k < 1:
-            raise ValueError("[knn] requires k > 0")
-        if self.k > MAX_RESULT_WINDOW:
-            raise ValueError(f"[knn] requires k <= {MAX_RESULT_WINDOW}")
+        if (self.k is None) == (self.min_score is None):
+            raise ValueError("[knn] requires exactly one of k and min_score")
+        if self.min_score is not None:
+            ms = self.min_score
+            if isinstance(ms, bool) or not isinstance(ms, (int, float)) or not math.isfinite(ms) or not ms > 0:
+                raise ValueError("[knn] requires min_score to be a finite number > 0")
+            self.min_score = float(ms)
+        else:
+            if not isinstance(self.k, int) or isinstance(self.k, bool) or self.k < 1:
+                raise ValueError("[knn] requires k > 0")
+            if self.k > MAX_RESULT_WINDOW:
+                raise ValueError(f"[knn] requires k <= {MAX_RESULT_WINDOW}")
         if not self.vector:
             raise ValueError("[knn] query vector is empty")
         if self.filter is not None:
@@ -210,7 +224,11 @@ class KnnQueryBuilder:
 
     # ---- XContent ------------------------------------------------------------------------------
     def to_xcontent(self) -> dict:
-        inner = {"vector": list(self.vector), "k": self.k}
+        inner = {"vector": list(self.vector)}
+        if self.min_score is not None:
+            inner["min_score"] = self.min_score
+        else:
+            inner["k"] = self.k
         if self.filter is not None:
             inner["filter"] = self.filter
         if self.boost != 1.0:
@@ -231,27 +249,32 @@ class KnnQueryBuilder:
         (name, inner), = fields.items()
         if not isinstance(inner, dict):
             raise ParsingException("[knn] field body must be an object")
-        unknown = set(inner) - {"vector", "k", "filter", "boost", "_name"}
+        unknown = set(inner) - {"vector", "k", "min_score", "filter", "boost", "_name"}
         if unknown:
             raise ParsingException(f"[knn] unknown field(s) {sorted(unknown)}")
-        if "vector" not in inner or "k" not in inner:
-            raise ParsingException("[knn] requires [vector] and [k]")
+        if "vector" not in inner or ("k" in inner) == ("min_score" in inner):
+            raise ParsingException("[knn] requires [vector] and exactly one of [k] and [min_score]")
+        if "min_score" in inner and inner["min_score"] is None:
+            raise ParsingException("[knn] requires min_score to be a finite number > 0")
         try:
-            return cls(name, list(inner["vector"]), inner["k"], inner.get("filter"), float(inner.get("boost", 1.0)),
-                       inner.get("_name"))
+            return cls(name, list(inner["vector"]), inner.get("k"), inner.get("filter"), float(inner.get("boost", 1.0)),
+                       inner.get("_name"), inner.get("min_score"))
         except ValueError as e:
             raise ParsingException(str(e)) from e
 
     # ---- transport serialisation (NamedWriteable: writeTo / StreamInput ctor) -------------------
+    # A k query's bytes are what they always were.  A min_score query writes k = 0 (never a valid k) and
+    # appends its threshold as one big-endian float after the last field.
     def write_to(self) -> bytes:
         name = self.field_name.encode()
         filt = b"" if self.filter is None else json.dumps(self.filter, sort_keys=True).encode()
         qn = b"" if self.query_name is None else self.query_name.encode()
         vec = np.asarray(self.vector, np.float32)
         return (struct.pack(">I", len(name)) + name + struct.pack(">I", len(vec)) + vec.astype(">f4").tobytes()
-                + struct.pack(">i", self.k) + struct.pack(">?", self.filter is not None)
+                + struct.pack(">i", self.k if self.min_score is None else 0) + struct.pack(">?", self.filter is not None)
                 + struct.pack(">I", len(filt)) + filt + struct.pack(">f", self.boost)
-                + struct.pack(">?", self.query_name is not None) + struct.pack(">I", len(qn)) + qn)
+                + struct.pack(">?", self.query_name is not None) + struct.pack(">I", len(qn)) + qn
+                + (b"" if self.min_score is None else struct.pack(">f", self.min_score)))
 
     @classmethod
     def read_from(cls, data: bytes) -> "KnnQueryBuilder":
@@ -271,7 +294,9 @@ class KnnQueryBuilder:
         boost = struct.unpack(">f", take(4))[0]
         has_qn = struct.unpack(">?", take(1))[0]
         qn = take(struct.unpack(">I", take(4))[0]).decode()
-        return cls(name, vec, k, json.loads(filt) if has_f else None, boost, qn if has_qn else None)
+        min_score = struct.unpack(">f", take(4))[0] if k == 0 else None
+        return cls(name, vec, k if k != 0 else None, json.loads(filt) if has_f else None, boost,
+                   qn if has_qn else None, min_score)
 
     # ---- toQuery ---------------------------------------------------------------------------------
     def do_to_query(self, ctx: QueryShardContext):
@@ -289,6 +314,11 @@ class KnnQueryBuilder:
             if ctx.doc_values is None:
                 raise QueryShardException("[knn] filter needs the shard's doc values")
             filt = lambda leaf, q=self.filter: _eval_filter(q, ctx, leaf)   # noqa: E731
+        if self.min_score is not None:
+            # [L] Float/ByteVectorSimilarityQuery(field, target, traversalSimilarity, resultSimilarity, filter):
+            # a flat field has no graph to traverse, so both similarities are min_score
+            cls = ByteVectorSimilarityQuery if ft.encoding == VectorEncoding.BYTE else FloatVectorSimilarityQuery
+            return cls(self.field_name, target, self.min_score, self.min_score, filt)
         cls = KnnByteVectorQuery if ft.encoding == VectorEncoding.BYTE else KnnFloatVectorQuery
         return cls(self.field_name, target, self.k, filt)
 

@@ -216,6 +216,23 @@ class GpuFlatVectorsReader:
                                    ptr(counts), ptr(visited)))
         return scores, docs, counts, visited
 
+    def search_threshold(self, targets, min_score, accept_bits: np.ndarray | None = None, cap: int = 1024):
+        """Every accepted vector scoring ≥ min_score (one per target, or a scalar for all), in doc order:
+        (docs[nq,cap], scores[nq,cap], count[nq], total[nq], visited[nq]) — osk_seg_search_threshold.
+        `total` is exact whatever `cap`; when total > cap the first cap hits in doc order come back."""
+        q = _as_query_array(targets, self.encoding, self.dim)
+        nq = q.shape[0]
+        ms = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32), (nq,)))
+        docs = np.empty((nq, cap), np.int32)
+        scores = np.empty((nq, cap), np.float32)
+        count = np.empty(nq, np.int32)
+        total = np.empty(nq, np.int64)
+        visited = np.empty(nq, np.int64)
+        ab = None if accept_bits is None else np.ascontiguousarray(accept_bits, dtype=np.uint64)
+        check(lib().osk_seg_search_threshold(self.handle, ptr(q), nq, ptr(ms), ptr(ab), cap, ptr(docs), ptr(scores),
+                                             ptr(count), ptr(total), ptr(visited)))
+        return docs, scores, count, total, visited
+
     def search(self, field: str, target, k: int, accept_docs: np.ndarray | None = None) -> TopDocs:
         """[L] KnnVectorsReader.search(field, target, KnnCollector(k), AcceptDocs) → the collector's
         topDocs(): segment-local docs, score desc / doc asc, totalHits = visited (EQUAL_TO)."""
@@ -414,12 +431,106 @@ class GpuKnnFloatVectorQuery(_GpuKnnVectorQuery, KnnFloatVectorQuery):
 class GpuKnnByteVectorQuery(_GpuKnnVectorQuery, KnnByteVectorQuery):
     encoding = VectorEncoding.BYTE
 
+# ------------------------------------------------------------------------------------------------
+# [L] AbstractVectorSimilarityQuery: every document at least this similar (OpenSearch k-NN `min_score`)
+# ------------------------------------------------------------------------------------------------
+class _VectorSimilarityQuery:
+    """[L] AbstractVectorSimilarityQuery(field, traversalSimilarity, resultSimilarity, filter) on a flat
+    (graph-less) field: a doc matches iff it is accepted (liveDocs ∩ filter) and its score is
+    ≥ resultSimilarity.  traversalSimilarity steers Lucene's graph traversal; a flat field has no graph, so
+    it is accepted (it must not exceed resultSimilarity, as in Lucene) and otherwise ignored.
+
+    `rewrite` takes Lucene's per-leaf route — one reader call per leaf, docBase added, leaves concatenated
+    in docBase order — and returns the matches in doc order with their scores and the exact total.  A leaf
+    whose hits exceed the first call's capacity is asked again with cap = total, so every hit comes back."""
+    encoding = VectorEncoding.FLOAT32
+    DEFAULT_CAP = 1024
+
+    def __init__(self, field: str, target, traversal_similarity: float, result_similarity: float, filter=None):
+        if traversal_similarity > result_similarity:
+            raise ValueError("traversalSimilarity should be <= resultSimilarity")
+        self.field = field
+        self.target = target
+        self.traversal_similarity = float(traversal_similarity)   # no graph: unused
+        self.result_similarity = float(result_similarity)
+        self.filter = filter          # callable(leaf) -> bool[max_doc], or None
+
+    _accept = _KnnVectorQuery._accept
+
+    def rewrite(self, leaves: Iterable[LeafReaderContext]) -> TopDocs:
+        hits, total = [], 0
+        for leaf in sorted((lf for lf in leaves if lf.reader.field == self.field), key=lambda lf: lf.doc_base):
+            acc = self._accept(leaf)
+            ab = None if acc is None else bits_from_bool(acc)
+            d, s, c, t, _ = leaf.reader.search_threshold(self.target, self.result_similarity, ab, self.DEFAULT_CAP)
+            if int(t[0]) > int(c[0]):
+                d, s, c, t, _ = leaf.reader.search_threshold(self.target, self.result_similarity, ab, int(t[0]))
+            n = int(c[0])
+            hits += [ScoreDoc(int(d[0, i]) + leaf.doc_base, float(s[0, i])) for i in range(n)]
+            total += int(t[0])
+        return TopDocs(TotalHits(total), hits)
+
+
+class FloatVectorSimilarityQuery(_VectorSimilarityQuery):
+    """[L] FloatVectorSimilarityQuery(field, float[] target, traversalSimilarity, resultSimilarity, filter)."""
+    encoding = VectorEncoding.FLOAT32
+
+
+class ByteVectorSimilarityQuery(_VectorSimilarityQuery):
+    """[L] ByteVectorSimilarityQuery(field, byte[] target, traversalSimilarity, resultSimilarity, filter)."""
+    encoding = VectorEncoding.BYTE
+
+
+class _GpuVectorSimilarityQuery(_VectorSimilarityQuery):
+    """The plugin's similarity query: ONE osk_view_search_threshold call per shard over the cached view of
+    all its leaves (_GpuKnnVectorQuery's cache and reader-closed eviction), each leaf's AcceptDocs pushed
+    down as a bitset.  Same result as the per-leaf route."""
+
+    def rewrite(self, leaves: Iterable[LeafReaderContext]) -> TopDocs:
+        leaves = [lf for lf in leaves if lf.reader.field == self.field]
+        if not leaves:
+            return TopDocs(TotalHits(0), [])
+        G = _GpuKnnVectorQuery
+        e = G._acquire_view(self, leaves)
+        try:
+            accept = [self._accept(lf) for lf in leaves]
+            if all(a is None for a in accept):
+                accept = None
+            d, s, c, t = e.view.search_threshold(self.target, self.result_similarity, accept, self.DEFAULT_CAP)
+            if int(t[0, 0]) > int(c[0, 0]):
+                d, s, c, t = e.view.search_threshold(self.target, self.result_similarity, accept, int(t[0, 0]))
+        finally:
+            G._release_view(e)
+        n = int(c[0, 0])
+        return TopDocs(TotalHits(int(t[0, 0])), [ScoreDoc(int(d[0, 0, i]), float(s[0, 0, i])) for i in range(n)])
+
+
+class GpuFloatVectorSimilarityQuery(_GpuVectorSimilarityQuery):
+    encoding = VectorEncoding.FLOAT32
+
+
+class GpuByteVectorSimilarityQuery(_GpuVectorSimilarityQuery):
+    encoding = VectorEncoding.BYTE
+
+
+def shard_similarity_query_phase(query: _VectorSimilarityQuery, leaves: Sequence[LeafReaderContext], from_: int,
+                                 size: int) -> TopDocs:
+    """The shard's query phase for a similarity query: a TopScoreDocCollector over the query's scorer with
+    numDocs = from+size (S/search/query/TopDocsCollectorContext.java:866-891) — hits by score desc, doc asc,
+    cut to from+size; totalHits = every match (EQUAL_TO).  (max_score = score_docs[0].score when there is one.)"""
+    matched = query.rewrite(leaves)
+    hits = sorted(matched.score_docs, key=lambda h: (-h.score, h.doc))[: from_ + size]
+    return TopDocs(TotalHits(matched.total_hits.value, Relation.EQUAL_TO), [ScoreDoc(h.doc, h.score) for h in hits])
+
 
 def shard_query_phase(query: _KnnVectorQuery, leaves: Sequence[LeafReaderContext], from_: int,
                       size: int) -> TopDocs:
     """The shard's query phase for a k-NN query: rewrite (ContextIndexSearcher.java:203-218), then
     a TopScoreDocCollector over the DocAndScoreQuery with numDocs = min(from+size, …)
-    (S/search/query/TopDocsCollectorContext.java:866-891).  totalHits = number of k-NN hits."""
+    (S/search/query/TopDocsCollectorContext.java:866-891).  totalHits = number of k-NN hits.
+    A similarity query ([L] AbstractVectorSimilarityQuery) takes shard_similarity_query_phase."""
+    if isinstance(query, _VectorSimilarityQuery):
+        return shard_similarity_query_phase(query, leaves, from_, size)
     rewritten = query.rewrite(leaves)
     hits = rewritten.score_docs[: from_ + size]
     return TopDocs(TotalHits(len(rewritten.score_docs)), [ScoreDoc(h.doc, h.score) for h in hits])
@@ -485,6 +596,36 @@ class DeviceShardSet:
                                     ptr(docs), ptr(shard), ptr(count), ptr(total), ptr(mx)))
         return scores, docs, shard, count, total, mx
 
+    def _accept_table(self, accept, keep: list):
+        if accept is None:
+            return None
+        ptrs = []
+        for a in accept:
+            if a is None:
+                ptrs.append(None)
+            else:
+                b = bits_from_bool(a)
+                keep.append(b)
+                ptrs.append(b.ctypes.data)
+        return (C.c_void_p * len(ptrs))(*ptrs)
+
+    def search_threshold(self, targets, min_score, accept=None, cap: int = 1024):
+        """Every accepted vector of each shard scoring ≥ min_score (one per target, or a scalar), shard-local
+        docs ascending: (docs[nq,S,cap], scores[nq,S,cap], count[nq,S], total[nq,S]) — osk_view_search_threshold.
+        accept: None or one bool[max_doc] (or None) per leaf."""
+        q = _as_query_array(targets, self.encoding, self.dim)
+        nq, S = q.shape[0], self.n_shards
+        ms = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32), (nq,)))
+        docs = np.empty((nq, S, cap), np.int32)
+        scores = np.empty((nq, S, cap), np.float32)
+        count = np.empty((nq, S), np.int32)
+        total = np.empty((nq, S), np.int64)
+        keep: list = []
+        acc_arr = self._accept_table(accept, keep)
+        check(lib().osk_view_search_threshold(self.handle, ptr(q), nq, ptr(ms), acc_arr, cap, ptr(docs), ptr(scores),
+                                              ptr(count), ptr(total)))
+        return docs, scores, count, total
+
     def stats(self) -> tuple[int, int]:
         """(searches that took the batched MFMA path, queries recomputed after a failed certificate)."""
         a, b = C.c_int64(), C.c_int64()
@@ -493,7 +634,7 @@ class DeviceShardSet:
 
     def counter(self, name: str) -> int:
         """A named counter of the view (osk_view_counter): "sq8_calls", "sq8_fallback_queries",
-        "sq8_rescored_rows", "mfma_calls", "mfma_fallback_queries"."""
+        "sq8_rescored_rows", "mfma_calls", "mfma_fallback_queries", "threshold_calls"."""
         v = C.c_int64()
         check(lib().osk_view_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
