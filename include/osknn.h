@@ -53,6 +53,10 @@
  *       [L] AbstractVectorSimilarityQuery (FloatVectorSimilarityQuery, ByteVectorSimilarityQuery) over a
  *       flat field: every accepted doc whose score is ≥ resultSimilarity, in doc order, with the exact
  *       count — OpenSearch's k-NN `min_score`.
+ *   osk_seg_set_parents / osk_seg_search_nested / osk_view_search_nested / osk_view_search_nested_device
+ *       [L] DiversifyingChildrenFloatKnnVectorQuery / DiversifyingChildrenByteKnnVectorQuery (exactSearch)
+ *       with the leaf's parent BitSetProducer: the k best parents, each represented by its best accepted
+ *       child — what OpenSearch k-NN builds for a `knn` query inside a `nested` query.
  *   osk_merge_device / osk_topdocs_merge
  *       The coordinator's reduce: S/action/search/SearchPhaseController.java:224-246 (mergeTopDocs →
  *       [L] TopDocs.merge(from, size, shardHits): score desc, then shardIndex asc, then doc asc),
@@ -294,7 +298,7 @@ int32_t osk_view_stats(osk_view* view, int64_t* batched_calls, int64_t* fallback
  * "sq8_fallback_queries" (queries where some tile's candidate
  * list overflowed past the certificate and the tile was re-scanned exactly), "sq8_exact_tiles"
  * (such tiles), "sq8_rescored_rows" (rows re-scored exactly, all calls), "select_calls" (searches
- * on the select path, k > 12), "threshold_calls" (similarity-threshold searches), "host_slots" (workspace slots the host entries have leased: 1 + replicas),
+ * on the select path, k > 12), "threshold_calls" (similarity-threshold searches), "nested_calls" (nested k-NN searches),"host_slots" (workspace slots the host entries have leased: 1 + replicas),
  * "host_batches" / "host_batched_requests" (opportunistic batching of concurrent host calls).  The
  * search counters sum over the view and the replica slots its host entries leased.  osk_view_profile /
  * osk_view_scan_time time the device-entry calls on this view object only (per-call host timing:
@@ -366,6 +370,53 @@ int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, 
                                          const float* d_min_scores, const uint64_t* const* d_accept,
                                          int32_t cap, int32_t* d_docs, float* d_scores, int32_t* d_count,
                                          int64_t* d_total, int64_t* d_visited, void* stream);
+
+/* ---- nested k-NN: the k best parents, each by its best child ----
+ * [L] DiversifyingChildrenFloatKnnVectorQuery / DiversifyingChildrenByteKnnVectorQuery.exactSearch (Lucene 10.3),
+ * which OpenSearch k-NN builds whenever a `knn` query sits inside a `nested` query: a document is split into
+ * chunks, each chunk a nested child doc with its own vector, and the search returns k DISTINCT parents.
+ *   families     a leaf has a parent bitset over [0, max_doc); the parent of a vector's doc d is nextSetBit(d),
+ *                inclusive (a parent doc that carries a vector is a family of one).  A family = the parent's
+ *                accepted children (AcceptDocs: liveDocs ∩ filter, pushed down as a bitset as in the k-NN entries).
+ *   best child   the highest score, among equal scores the lowest child doc; a NaN score is never best; a family
+ *                without an accepted non-NaN child does not appear.
+ *   result       the k best families by (best child's score desc, best child's doc asc), returned as CHILD docs
+ *                with their scores in exactly the k-NN entries' layout: unused slots -inf / INT32_MAX, count =
+ *                families returned (≤ k), visited = accepted vectors scored (NaN rows included).  Joining a child
+ *                to its parent stays with the caller ([L] ToParentBlockJoinQuery).
+ *   scores       bit-identical to osk_seg_search's for the same row (device summation order).
+ * Exact: one brute-force pass of the fp32 / int8 streaming scan.  Two limits:
+ *   1 ≤ k ≤ 64 (the streaming scan's lists); a larger k returns OSK_ERR_UNSUPPORTED — routing large k through
+ *   the select path is the follow-up;
+ *   the certified int8 / 6-bit prefilters are not used, so a float32 search runs at the fp32 scan's rate.
+ * A null pointer, n_queries < 1 or k < 1 is OSK_ERR_INVALID (k > 64: OSK_ERR_UNSUPPORTED) before the device is
+ * touched; without a device the entries return OSK_ERR_NO_DEVICE.  Multi-GPU nested search
+ * (osk_shards_search_merge*) is not provided. */
+
+/* Register the leaf's parent bitset, once per segment ([L] the BitSetProducer Lucene caches per segment; a
+ * vector field lives under one nested path, so a segment has one set).  parent_bits: ceil(max_doc/64) host
+ * words, LSB-first.  Builds the segment's device-side row→parent table (4 B per row, counted by
+ * osk_seg_footprint).  OSK_ERR_INVALID if a vector's doc lies after the last parent, if the bitset is empty,
+ * or on a second call for the segment. */
+int32_t osk_seg_set_parents(osk_seg* seg, const uint64_t* parent_bits);
+/* Number of parent docs registered (0 = none). */
+int32_t osk_seg_parents(const osk_seg* seg, int64_t* n_parents);
+/* Nested k-NN over ONE leaf: osk_seg_search's arguments and output layout (docs segment-local child docs). */
+int32_t osk_seg_search_nested(osk_seg* seg, const void* queries, int32_t n_queries, int32_t k,
+                              const uint64_t* accept_bits, float* out_scores, int32_t* out_docs,
+                              int32_t* out_count, int64_t* out_visited);
+/* Nested k-NN per shard of a view, then the coordinator reduce: osk_view_search's arguments and output layout
+ * (docs shard-local child docs, docBase added).  OSK_ERR_INVALID when a segment of the view has no parents
+ * registered.  The view's own tables are built at the first nested search or by osk_view_warm. */
+int32_t osk_view_search_nested(osk_view* view, const void* queries, int32_t n_queries, int32_t k,
+                               int32_t from, int32_t size, const uint64_t* const* accept,
+                               float* out_scores, int32_t* out_docs, int32_t* out_shard_index,
+                               int32_t* out_count, int64_t* out_total_hits, float* out_max_score);
+/* The per-shard part with DEVICE buffers, asynchronous on `stream`: osk_view_search_device's arguments, rules
+ * and key layout, so osk_merge_device / osk_merge_device_ranked take its output unchanged. */
+int32_t osk_view_search_nested_device(osk_view* view, const void* d_queries, int32_t n_queries, int32_t k,
+                                      const uint64_t* const* d_accept, uint64_t* d_shard_keys,
+                                      int32_t* d_shard_counts, int64_t* d_visited, void* stream);
 
 /* [L] TopDocs.merge(from, size, shardHits) + TopDocsStats over host arrays (no device).
  *   shard_counts[s] hits of list s; shard_scores/shard_docs row s holds them at offset s*stride

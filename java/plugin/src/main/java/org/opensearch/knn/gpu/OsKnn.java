@@ -97,6 +97,29 @@ final class OsKnn {
         FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
             ADDRESS, ADDRESS, ADDRESS, ADDRESS));
 
+    // Nested k-NN ([L] DiversifyingChildrenFloat/ByteKnnVectorQuery on a flat field; knn inside nested)
+    // int32_t osk_seg_set_parents(osk_seg* seg, const uint64_t* parent_bits)
+    static final MethodHandle SEG_SET_PARENTS = h("osk_seg_set_parents", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
+    // int32_t osk_seg_parents(const osk_seg* seg, int64_t* n_parents)
+    static final MethodHandle SEG_PARENTS = h("osk_seg_parents", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
+    // int32_t osk_seg_search_nested(osk_seg* seg, const void* queries, int32_t n_queries, int32_t k,
+    //     const uint64_t* accept_bits, float* out_scores, int32_t* out_docs, int32_t* out_count, int64_t* out_visited)
+    static final MethodHandle SEG_SEARCH_NESTED = h("osk_seg_search_nested", FunctionDescriptor.of(JAVA_INT,
+        ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS),
+        Linker.Option.critical(true));   // heap arrays are passed directly
+    // int32_t osk_view_search_nested(osk_view* view, const void* queries, int32_t n_queries, int32_t k, int32_t from,
+    //     int32_t size, const uint64_t* const* accept, float* out_scores, int32_t* out_docs, int32_t* out_shard_index,
+    //     int32_t* out_count, int64_t* out_total_hits, float* out_max_score)
+    static final MethodHandle VIEW_SEARCH_NESTED = h("osk_view_search_nested", FunctionDescriptor.of(JAVA_INT,
+        ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+        ADDRESS, ADDRESS, ADDRESS));
+    // int32_t osk_view_search_nested_device(osk_view* view, const void* d_queries, int32_t n_queries, int32_t k,
+    //     const uint64_t* const* d_accept, uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited,
+    //     void* stream)
+    static final MethodHandle VIEW_SEARCH_NESTED_DEVICE = h("osk_view_search_nested_device",
+        FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+            ADDRESS));
+
     // multi-GPU node (INTEGRATION.md §4)
     static final MethodHandle COMM_UNIQUE_ID = h("osk_comm_unique_id", FunctionDescriptor.of(JAVA_INT, ADDRESS));
     static final MethodHandle COMM_INIT_RANK = h("osk_comm_init_rank", FunctionDescriptor.of(JAVA_INT,
@@ -180,6 +203,65 @@ final class OsKnn {
         try {
             check((int) VIEW_SEARCH_THRESHOLD_DEVICE.invokeExact(view, dQueries, nQueries, dMinScores, dAccept, cap,
                 dDocs, dScores, dCount, dTotal, dVisited, stream));
+        } catch (Throwable t) {
+            throw wrap(t);
+        }
+    }
+
+    /** Register the leaf's parent bitset ([L] the nested path's BitSetProducer), once per segment:
+     *  ceil(maxDoc/64) words, LSB-first (osknn.h). */
+    static void segSetParents(MemorySegment seg, MemorySegment parentBits) throws IOException {
+        try {
+            check((int) SEG_SET_PARENTS.invokeExact(seg, parentBits));
+        } catch (Throwable t) {
+            throw wrap(t);
+        }
+    }
+
+    /** Number of parent docs registered on the segment (0 = none). */
+    static long segParents(MemorySegment seg) throws IOException {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment n = a.allocate(JAVA_LONG);
+            check((int) SEG_PARENTS.invokeExact(seg, n));
+            return n.get(JAVA_LONG, 0);
+        } catch (Throwable t) {
+            throw wrap(t);
+        }
+    }
+
+    /** [L] DiversifyingChildrenFloat/ByteKnnVectorQuery.exactSearch over one leaf: the k best parents, each by its
+     *  best accepted child — child docs and scores in segSearch's layout; k ≤ 64 (osknn.h). */
+    static void segSearchNested(MemorySegment seg, MemorySegment queries, int nQueries, int k, MemorySegment acceptBits,
+                                MemorySegment outScores, MemorySegment outDocs, MemorySegment outCount,
+                                MemorySegment outVisited) throws IOException {
+        try {
+            check((int) SEG_SEARCH_NESTED.invokeExact(seg, queries, nQueries, k, acceptBits, outScores, outDocs,
+                outCount, outVisited));
+        } catch (Throwable t) {
+            throw wrap(t);
+        }
+    }
+
+    /** The same per shard of a view, then the coordinator reduce: viewSearch's outputs, docs = child docs. */
+    static void viewSearchNested(MemorySegment view, MemorySegment queries, int nQueries, int k, int from, int size,
+                                 MemorySegment accept, MemorySegment outScores, MemorySegment outDocs,
+                                 MemorySegment outShardIndex, MemorySegment outCount, MemorySegment outTotalHits,
+                                 MemorySegment outMaxScore) throws IOException {
+        try {
+            check((int) VIEW_SEARCH_NESTED.invokeExact(view, queries, nQueries, k, from, size, accept, outScores,
+                outDocs, outShardIndex, outCount, outTotalHits, outMaxScore));
+        } catch (Throwable t) {
+            throw wrap(t);
+        }
+    }
+
+    /** The per-shard part with device buffers, asynchronous on {@code stream} (NULL = the library's stream). */
+    static void viewSearchNestedDevice(MemorySegment view, MemorySegment dQueries, int nQueries, int k,
+                                       MemorySegment dAccept, MemorySegment dShardKeys, MemorySegment dShardCounts,
+                                       MemorySegment dVisited, MemorySegment stream) throws IOException {
+        try {
+            check((int) VIEW_SEARCH_NESTED_DEVICE.invokeExact(view, dQueries, nQueries, k, dAccept, dShardKeys,
+                dShardCounts, dVisited, stream));
         } catch (Throwable t) {
             throw wrap(t);
         }

@@ -163,6 +163,7 @@ osk_seg::~osk_seg() {
     if (d_q8t) (void)hipFree(d_q8t);
     if (d_q8auxt) (void)hipFree(d_q8auxt);
     if (d_q8w) (void)hipFree(d_q8w);
+    if (d_row_parent) (void)hipFree(d_row_parent);
     if (d_q6 || d_q6aux) {   // stream-ordered pool allocations (ensure_sq8_seg); the hipFree calls above
         int cur = -1;         // synchronised the device, so nothing reads them any more
         (void)hipGetDevice(&cur);
@@ -187,6 +188,7 @@ int64_t osk_seg::hbm_bytes() const {
     if (d_q8auxt) b += std::max<int64_t>(1, (n_rows + 15) / 16) * kAuxGroupF4 * 16;
     if (d_q8w) b += std::max<int64_t>(1, (n_rows + 15) / 16) * sq8_wide_ks(units8) * 1024;
     if (d_q6) b += sq6_bytes(n_rows, dim);
+    if (d_row_parent) b += n * 4;
     return b;
 }
 
@@ -225,6 +227,7 @@ int32_t ensure_sq8(osk_view* v, hipStream_t st);
 int32_t ensure_sq8t(osk_view* v, hipStream_t st);
 int32_t ensure_sq8w(osk_view* v, hipStream_t st);
 int32_t ensure_mfma(osk_view* v, hipStream_t st);
+int32_t ensure_nested(osk_view* v, hipStream_t st);
 
 int32_t seg_finish(osk_seg* s, const int32_t* ord_to_doc, hipStream_t st) {
     // row norms
@@ -821,13 +824,20 @@ int32_t osk_view_warm(osk_view* view, int32_t what) {
         int32_t rc = osk_seg_warm(s, what);
         if (rc) return rc;
     }
-    if (view->enc != ENC_FLOAT32 || view->n_tiles == 0) return OSK_OK;
+    bool all_parents = true;   // the nested search's view tables, once every segment has its parents
+    for (osk_seg* s : view->segs) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        all_parents = all_parents && s->n_parents > 0;
+    }
+    if ((view->enc != ENC_FLOAT32 || view->n_tiles == 0) && !all_parents) return OSK_OK;
     int32_t rc = check_device(view->device);
     if (rc) return rc;
     hipStream_t st = device_stream(view->device);
     std::lock_guard<std::mutex> lk(view->mu);
     rc = order_after_last(view, st);
     if (rc) return rc;
+    if (all_parents && (rc = ensure_nested(view, st)) != OSK_OK) return rc;
+    if (view->enc != ENC_FLOAT32 || view->n_tiles == 0) return OSK_OK;
     if (what & (OSK_WARM_PREFILTER | OSK_WARM_PREFILTER_MFMA)) {
         rc = ensure_sq8(view, st);
         if (rc) return rc;
@@ -922,6 +932,47 @@ int32_t stream_search(osk_view* v, const void* qpad, const void* qnorm, int nq, 
     OSK_HIP(launch_merge_shards(v->ws_cand.as<uint64_t>(), v->n_tiles,
                                 v->d_shard_tile_begin.as<int32_t>(), v->n_shards, nq, k,
                                 d_shard_keys, d_shard_counts, st));
+    return OSK_OK;
+}
+
+// The view's tables of the nested search (caller holds v->mu): every segment's row→parent table and its
+// parent-slot base — segments in the tile table's order (by shard, then segment), so a shard's parent slots
+// are contiguous — and the parent tiles: runs of ≤ kNestPtile slots of one shard.  Built once.
+int32_t ensure_nested(osk_view* v, hipStream_t st) {
+    if (v->nest_ready) return OSK_OK;
+    const int ns = (int)v->segs.size(), S = v->n_shards;
+    std::vector<NestSeg> nsegs(ns);
+    std::vector<NestPtile> ptiles;
+    std::vector<int32_t> spb(S + 1, 0);
+    int64_t slots = 0;
+    for (int sh = 0; sh < S; ++sh) {
+        spb[sh] = (int32_t)ptiles.size();
+        const int64_t first = slots;
+        for (int i = 0; i < ns; ++i) {
+            if (v->seg_shard[i] != sh) continue;
+            osk_seg* sg = v->segs[i];
+            std::lock_guard<std::mutex> lk(sg->mu);
+            OSK_REQUIRE(sg->n_parents > 0 && sg->d_row_parent != nullptr,
+                        "nested search: a segment of the view has no parents registered (osk_seg_set_parents)");
+            nsegs[i] = NestSeg{sg->d_row_parent, slots};
+            slots += sg->n_parents;
+        }
+        for (int64_t b = first; b < slots; b += kNestPtile)
+            ptiles.push_back(NestPtile{b, std::min<int64_t>(b + kNestPtile, slots)});
+    }
+    spb[S] = (int32_t)ptiles.size();
+    OSK_REQUIRE(ptiles.size() < (size_t)(1 << 24), "too many parent tiles");
+    OSK_HIP(v->d_nest_segs.reserve(sizeof(NestSeg) * ns));
+    OSK_HIP(v->d_ptiles.reserve(sizeof(NestPtile) * std::max<size_t>(1, ptiles.size())));
+    OSK_HIP(v->d_shard_ptile_begin.reserve(sizeof(int32_t) * (S + 1)));
+    OSK_HIP(hipMemcpyAsync(v->d_nest_segs.p, nsegs.data(), sizeof(NestSeg) * ns, hipMemcpyHostToDevice, st));
+    if (!ptiles.empty())
+        OSK_HIP(hipMemcpyAsync(v->d_ptiles.p, ptiles.data(), sizeof(NestPtile) * ptiles.size(), hipMemcpyHostToDevice, st));
+    OSK_HIP(hipMemcpyAsync(v->d_shard_ptile_begin.p, spb.data(), sizeof(int32_t) * (S + 1), hipMemcpyHostToDevice, st));
+    OSK_HIP(hipStreamSynchronize(st));   // the sources are locals
+    v->nest_parents = slots;
+    v->n_ptiles = (int)ptiles.size();
+    v->nest_ready = true;
     return OSK_OK;
 }
 
@@ -2217,6 +2268,73 @@ int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const 
     return OSK_OK;
 }
 
+// Core of osk_view_search_nested_device (caller holds the view mutex; device already set): passes of up to
+// kMaxNQ queries, each a clear of the pass's best-child keys, one corpus read (nest_scan) and the parent
+// tiles' top k (nest_topk); then merge_shards over the parent tiles, as over scan tiles.
+int32_t view_nested_device(osk_view* v, const void* d_queries, int nq, int k, const uint64_t* const* d_accept,
+                           uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st) {
+    OSK_REQUIRE(nq >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(k >= 1, "k must be >= 1");
+    OSK_REQUIRE(d_queries && d_shard_keys && d_shard_counts, "null device buffer");
+    if (k > kScanMaxK) {
+        set_error("nested search supports k <= 64 (the streaming scan's lists); larger k is not implemented");
+        return OSK_ERR_UNSUPPORTED;
+    }
+    int32_t rc = order_after_last(v, st);
+    if (rc) return rc;
+    if ((rc = ensure_nested(v, st)) != OSK_OK) return rc;
+    if (v->n_tiles == 0) {   // nothing staged: every shard returns zero hits
+        OSK_HIP(hipMemsetAsync(d_shard_keys, 0, sizeof(uint64_t) * nq * v->n_shards * k, st));
+        OSK_HIP(hipMemsetAsync(d_shard_counts, 0, sizeof(int32_t) * nq * v->n_shards, st));
+        if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
+        v->nest_calls += 1;
+        return OSK_OK;
+    }
+    static const int kLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12},
+                                  {32, 8}, {64, 8}, {64, 16}};
+    const int UP = kLV[v->cfg][0] * kLV[v->cfg][1];
+    const int nq_pad = (nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;
+    const int64_t elem = v->enc == ENC_FLOAT32 ? 4 : 1;
+    const size_t P = (size_t)v->nest_parents;
+    OSK_HIP(v->ws_q.reserve((size_t)nq_pad * UP * 16));
+    OSK_HIP(v->ws_nest_best.reserve(sizeof(uint64_t) * (size_t)std::min(nq, kMaxNQ) * P));
+    OSK_HIP(v->ws_nest_cand.reserve(sizeof(uint64_t) * (size_t)nq * v->n_ptiles * k));
+    OSK_HIP(launch_prep_queries(d_queries, (int64_t)v->dim * elem, nq, v->ws_q.p, UP, nq_pad, st));
+    if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
+    v->profile = v->profile_every > 0 && v->profile_tick++ % (uint64_t)v->profile_every == 0;
+    if (v->profile && (rc = profile_begin(v, st, false)) != OSK_OK) return rc;
+
+    NestParams p{};
+    p.segs = v->d_segs.as<SegDev>();
+    p.tiles = v->d_tiles.as<TileDev>();
+    p.nsegs = v->d_nest_segs.as<NestSeg>();
+    p.accept = d_accept;
+    p.best = v->ws_nest_best.as<unsigned long long>();
+    p.visited = reinterpret_cast<unsigned long long*>(d_visited);
+    p.ptiles = v->d_ptiles.as<NestPtile>();
+    p.cand = v->ws_nest_cand.as<uint64_t>();
+    p.n_parents = v->nest_parents;
+    p.n_tiles = v->n_tiles;
+    p.n_ptiles = v->n_ptiles;
+    p.units = v->units;
+    p.k = k;
+    p.sim = v->sim;
+    p.dim = v->dim;
+    for (int q0 = 0; q0 < nq; q0 += kMaxNQ) {
+        p.q0 = q0;
+        p.q_count = std::min(kMaxNQ, nq - q0);
+        p.q = v->ws_q.as<char>() + (size_t)q0 * UP * 16;
+        OSK_HIP(hipMemsetAsync(p.best, 0, sizeof(uint64_t) * (size_t)p.q_count * P, st));
+        OSK_HIP(launch_nest_scan(v->enc, v->cfg, p, st, launch_ev_start(v, q0), launch_ev_stop(v, q0, nq)));
+        OSK_HIP(launch_nest_topk(p, st));
+    }
+    if ((rc = profile_end(v, st, false)) != OSK_OK) return rc;
+    OSK_HIP(launch_merge_shards(v->ws_nest_cand.as<uint64_t>(), v->n_ptiles, v->d_shard_ptile_begin.as<int32_t>(),
+                                v->n_shards, nq, k, d_shard_keys, d_shard_counts, st));
+    v->nest_calls += 1;
+    return OSK_OK;
+}
+
 }  // namespace osk
 
 extern "C" {
@@ -2254,6 +2372,104 @@ int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, 
     std::lock_guard<std::mutex> lk(view->mu);
     return view_threshold_device(view, d_queries, n_queries, d_min_scores, d_accept, cap, d_docs, d_scores, d_count,
                                  d_total, d_visited, st);
+    OSK_GUARD_END
+}
+
+// The argument rules every nested entry checks before the device is touched (k ≤ kScanMaxK: the lists of
+// the streaming scan; larger k through the select path is not implemented).
+static int32_t nested_args(int32_t n_queries, int32_t k) {
+    OSK_REQUIRE(n_queries >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(k >= 1, "k must be >= 1");
+    if (k > kScanMaxK) {
+        set_error("nested search supports k <= 64 (the streaming scan's lists); larger k is not implemented");
+        return OSK_ERR_UNSUPPORTED;
+    }
+    return OSK_OK;
+}
+
+int32_t osk_view_search_nested_device(osk_view* view, const void* d_queries, int32_t n_queries, int32_t k,
+                                      const uint64_t* const* d_accept, uint64_t* d_shard_keys,
+                                      int32_t* d_shard_counts, int64_t* d_visited, void* stream) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(view != nullptr, "view is null");
+    OSK_REQUIRE(d_queries && d_shard_keys && d_shard_counts, "null device buffer");
+    int32_t rc = nested_args(n_queries, k);
+    if (rc) return rc;
+    rc = any_device();
+    if (rc) return rc;
+    rc = check_device(view->device);
+    if (rc) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(view->device);
+    std::lock_guard<std::mutex> lk(view->mu);
+    return view_nested_device(view, d_queries, n_queries, k, d_accept, d_shard_keys, d_shard_counts, d_visited, st);
+    OSK_GUARD_END
+}
+
+int32_t osk_seg_set_parents(osk_seg* seg, const uint64_t* parent_bits) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(seg != nullptr && parent_bits != nullptr, "null argument");
+    int32_t rc = any_device();
+    if (rc) return rc;
+    rc = check_device(seg->device);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(seg->mu);
+    OSK_REQUIRE(seg->n_parents == 0, "the segment's parents are already registered");
+    const int64_t n_words = ((int64_t)seg->max_doc + 63) / 64;
+    // word_rank[w] = parent bits in words [0, w); bits at or past max_doc do not count
+    std::vector<uint64_t> bits(std::max<int64_t>(1, n_words), 0ull);
+    std::vector<int32_t> rank(std::max<int64_t>(1, n_words), 0);
+    int64_t total = 0, last = -1;
+    for (int64_t w = 0; w < n_words; ++w) {
+        uint64_t m = parent_bits[w];
+        const int64_t left = (int64_t)seg->max_doc - w * 64;
+        if (left < 64) m &= (1ull << left) - 1ull;
+        bits[w] = m;
+        rank[w] = (int32_t)total;
+        total += __builtin_popcountll(m);
+        if (m) last = w * 64 + 63 - __builtin_clzll(m);
+    }
+    OSK_REQUIRE(total > 0, "the parent bitset is empty");
+    hipStream_t st = device_stream(seg->device);
+    int32_t last_doc = -1;   // the last vector's doc
+    if (seg->n_rows > 0) {
+        if (seg->d_ord_to_doc)
+            OSK_HIP(hipMemcpy(&last_doc, seg->d_ord_to_doc + (seg->n_rows - 1), sizeof(int32_t), hipMemcpyDeviceToHost));
+        else
+            last_doc = (int32_t)(seg->n_rows - 1);
+    }
+    OSK_REQUIRE((int64_t)last_doc <= last, "a vector's doc lies after the last parent doc");
+    int32_t* rp = nullptr;
+    OSK_HIP(hipMalloc(&rp, std::max<int64_t>(1, seg->n_rows) * sizeof(int32_t)));
+    if (seg->n_rows > 0) {
+        DevBuf d_bits, d_rank;
+        hipError_t e = d_bits.reserve(bits.size() * 8);
+        if (e == hipSuccess) e = d_rank.reserve(rank.size() * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_bits.p, bits.data(), bits.size() * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_rank.p, rank.data(), rank.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = launch_nest_parents(d_bits.as<uint64_t>(), d_rank.as<int32_t>(), n_words, seg->d_ord_to_doc,
+                                    seg->n_rows, rp, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the temporaries are freed on return)
+        if (e != hipSuccess) {
+            (void)hipFree(rp);
+            set_error(std::string("osk_seg_set_parents: ") + hipGetErrorString(e));
+            return OSK_ERR_DEVICE;
+        }
+    }
+    seg->d_row_parent = rp;
+    seg->n_parents = total;
+    return OSK_OK;
+    OSK_GUARD_END
+}
+
+int32_t osk_seg_parents(const osk_seg* seg, int64_t* n_parents) {
+    OSK_GUARD_BEGIN
+    OSK_REQUIRE(seg != nullptr && n_parents != nullptr, "null argument");
+    std::lock_guard<std::mutex> lk(const_cast<osk_seg*>(seg)->mu);
+    *n_parents = seg->n_parents;
+    return OSK_OK;
     OSK_GUARD_END
 }
 
@@ -2417,7 +2633,7 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
                      n == "sq8_rows_quarter_end_cycles" || n == "sq8_rows_first_wait_cycles" ||
                      n == "sq8_rows_setup_barrier_cycles" || n == "sq8_rows_setup_fragment_cycles";
     OSK_REQUIRE(dev || n == "mfma_calls" || n == "mfma_fallback_queries" || n == "sq8_calls" || n == "sq6_calls" ||
-                    n == "select_calls" || n == "sq8_wide_calls" || n == "threshold_calls",
+                    n == "select_calls" || n == "sq8_wide_calls" || n == "threshold_calls" || n == "nested_calls",
                 "unknown counter: " + n);
     // summed over the view and the replicas its host entries leased
     int64_t sum = 0;
@@ -2446,7 +2662,8 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
         } else {
             sum += n == "mfma_calls" ? s->mfma_calls : n == "mfma_fallback_queries" ? s->mfma_fallback_queries
                  : n == "sq8_calls" ? s->sq8_calls : n == "sq6_calls" ? s->sq6_calls
-                 : n == "sq8_wide_calls" ? s->sq8w_calls : n == "threshold_calls" ? s->thr_calls : s->sel_calls;
+                 : n == "sq8_wide_calls" ? s->sq8w_calls : n == "threshold_calls" ? s->thr_calls
+                 : n == "nested_calls" ? s->nest_calls : s->sel_calls;
         }
     }
     *value = sum;
@@ -2474,7 +2691,7 @@ int32_t osk_view_scan_time(osk_view* v, double* total_ms, int64_t* calls) {
 static int32_t view_search_host(osk_view* v, const void* queries, int32_t n_queries, int32_t k, int32_t from,
                                 int32_t size, const uint64_t* const* accept, float* out_scores,
                                 int32_t* out_docs, int32_t* out_shard_index, int32_t* out_count,
-                                int64_t* out_total_hits, float* out_max_score) {
+                                int64_t* out_total_hits, float* out_max_score, bool nested = false) {
     OSK_GUARD_BEGIN
     clear_error();
     OSK_REQUIRE(v != nullptr && queries != nullptr, "null argument");
@@ -2529,8 +2746,10 @@ static int32_t view_search_host(osk_view* v, const void* queries, int32_t n_quer
     OSK_HIP(hipMemcpyAsync(v->ws_qin.p, queries, qbytes, hipMemcpyHostToDevice, st));
     OSK_HIP(v->ws_keys.reserve(sizeof(uint64_t) * (size_t)nq * S * k));
     OSK_HIP(v->ws_counts.reserve(sizeof(int32_t) * (size_t)nq * S));
-    rc = view_search_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
-                            v->ws_counts.as<int32_t>(), nullptr, st);
+    rc = nested ? view_nested_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
+                                     v->ws_counts.as<int32_t>(), nullptr, st)
+                : view_search_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
+                                     v->ws_counts.as<int32_t>(), nullptr, st);
     if (rc) return rc;
     // outputs: scores f32 | docs i32 | shard i32 | count i32 | total i64 | max f32
     const size_t n_out = (size_t)nq * size;
@@ -2565,7 +2784,7 @@ static int32_t view_search_host(osk_view* v, const void* queries, int32_t n_quer
 
 static int32_t seg_search_host(osk_seg* seg, const void* queries, int32_t n_queries, int32_t k,
                                const uint64_t* accept_bits, float* out_scores, int32_t* out_docs,
-                               int32_t* out_count, int64_t* out_visited) {
+                               int32_t* out_count, int64_t* out_visited, bool nested = false) {
     OSK_GUARD_BEGIN
     clear_error();
     OSK_REQUIRE(seg != nullptr && queries != nullptr, "null argument");
@@ -2617,8 +2836,10 @@ static int32_t seg_search_host(osk_seg* seg, const void* queries, int32_t n_quer
     OSK_HIP(v->ws_keys.reserve(sizeof(uint64_t) * (size_t)nq * k));
     OSK_HIP(v->ws_counts.reserve(sizeof(int32_t) * (size_t)nq));
     OSK_HIP(v->ws_visited.reserve(sizeof(int64_t)));
-    rc = view_search_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
-                            v->ws_counts.as<int32_t>(), v->ws_visited.as<int64_t>(), st);
+    rc = nested ? view_nested_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
+                                     v->ws_counts.as<int32_t>(), v->ws_visited.as<int64_t>(), st)
+                : view_search_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
+                                     v->ws_counts.as<int32_t>(), v->ws_visited.as<int64_t>(), st);
     if (rc) return rc;
     const size_t kb = sizeof(uint64_t) * (size_t)nq * k, cb = sizeof(int32_t) * nq;
     OSK_HIP(v->h_stage.reserve(kb + cb + 8));
@@ -2970,6 +3191,43 @@ int32_t osk_seg_search_threshold(osk_seg* seg, const void* queries, int32_t n_qu
     if (rc) return rc;
     for (int q = 0; out_visited && q < n_queries; ++q) out_visited[q] = visited;
     return OSK_OK;
+    OSK_GUARD_END
+}
+
+// Nested k-NN over a view / one segment, host buffers (synchronous): the host k-NN entries' route — a leased
+// workspace slot, the coordinator reduce — with the per-shard top k taken over parents; never batched with
+// other callers.
+int32_t osk_view_search_nested(osk_view* view, const void* queries, int32_t n_queries, int32_t k, int32_t from,
+                               int32_t size, const uint64_t* const* accept, float* out_scores, int32_t* out_docs,
+                               int32_t* out_shard_index, int32_t* out_count, int64_t* out_total_hits,
+                               float* out_max_score) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(view != nullptr && queries != nullptr, "null argument");
+    OSK_REQUIRE(out_scores && out_docs && out_shard_index && out_count && out_total_hits && out_max_score,
+                "null output");
+    OSK_REQUIRE(from >= 0 && size >= 1, "bad from/size");
+    int32_t rc = nested_args(n_queries, k);
+    if (rc) return rc;
+    rc = any_device();
+    if (rc) return rc;
+    return view_search_host(view, queries, n_queries, k, from, size, accept, out_scores, out_docs, out_shard_index,
+                            out_count, out_total_hits, out_max_score, true);
+    OSK_GUARD_END
+}
+
+int32_t osk_seg_search_nested(osk_seg* seg, const void* queries, int32_t n_queries, int32_t k,
+                              const uint64_t* accept_bits, float* out_scores, int32_t* out_docs, int32_t* out_count,
+                              int64_t* out_visited) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(seg != nullptr && queries != nullptr, "null argument");
+    OSK_REQUIRE(out_scores && out_docs && out_count, "null output");
+    int32_t rc = nested_args(n_queries, k);
+    if (rc) return rc;
+    rc = any_device();
+    if (rc) return rc;
+    return seg_search_host(seg, queries, n_queries, k, accept_bits, out_scores, out_docs, out_count, out_visited, true);
     OSK_GUARD_END
 }
 

@@ -530,6 +530,47 @@ hipError_t launch_thr_scan(int enc, int cfg, const ThrParams& p, hipStream_t s, 
                            hipEvent_t ev_stop = nullptr);
 hipError_t launch_thr_offsets(const ThrParams& p, hipStream_t s);
 hipError_t launch_thr_emit(int enc, int cfg, const ThrParams& p, hipStream_t s);
+// ---- nested k-NN (osk_nested.hip): the best accepted child of each parent, then the k best parents ----
+// [L] DiversifyingChildrenFloat/ByteKnnVectorQuery.exactSearch.  One corpus pass (nest_scan_*: scan_f32 /
+// scan_i8 with the wave top-k list replaced by a 64-bit atomic max of the hit key into best[query][parent
+// slot]), a top k per parent tile (nest_topk), then merge_shards over the parent tiles.  At most kMaxNQ
+// queries share a corpus pass; k ≤ kScanMaxK.
+constexpr int kNestPtile = 4096;     // parent slots per nest_topk workgroup
+struct NestSeg {                     // per segment of a view
+    const int32_t* row_parent;       // [n_rows] rank of the row's parent among the segment's parents
+    int64_t pbase;                   // the segment's first parent slot in the view (a shard's are contiguous)
+};
+struct NestPtile {
+    int64_t begin, end;              // parent slots [begin, end)
+};
+struct NestParams {
+    const SegDev* segs;
+    const TileDev* tiles;
+    const NestSeg* nsegs;            // [n_segs]
+    const uint64_t* const* accept;   // as ScanParams
+    const void* q;                   // this pass's queries, each padded to L*V units (zeros)
+    unsigned long long* best;        // [q_count][n_parents] best child key per parent slot (0 = none; cleared before the scan)
+    unsigned long long* visited;     // [n_segs] or null (counted by the q0 == 0 pass only)
+    const NestPtile* ptiles;         // [n_ptiles] runs of one shard's parent slots, ≤ kNestPtile each
+    uint64_t* cand;                  // [n_queries][n_ptiles][k] per-parent-tile candidate keys
+    int64_t n_parents;               // parent slots of the view
+    int n_tiles;
+    int n_ptiles;
+    int q0;                          // global index of this pass's first query
+    int q_count;                     // queries in this pass (≤ kMaxNQ)
+    int units;
+    int k;
+    int sim;
+    int dim;
+};
+// Every launcher checks its grid, LDS and arguments and returns hipErrorInvalidValue instead of launching.
+// row_parent[row] = number of parent bits strictly below the row's doc (= the rank of nextSetBit(doc)):
+// word_rank[w] = parent bits in words [0, w), plus a popcount of the row's masked word.
+hipError_t launch_nest_parents(const uint64_t* parent_bits, const int32_t* word_rank, int64_t n_words,
+                               const int32_t* ord_to_doc, int64_t n_rows, int32_t* row_parent, hipStream_t s);
+hipError_t launch_nest_scan(int enc, int cfg, const NestParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
+                            hipEvent_t ev_stop = nullptr);
+hipError_t launch_nest_topk(const NestParams& p, hipStream_t s);
 hipError_t launch_row_norms_f32(const float4* rows, int64_t n_rows, int units, int cfg,
                                 float* out, hipStream_t s);
 hipError_t launch_row_norms_i8(const int4* rows, int64_t n_rows, int units, int32_t* out,

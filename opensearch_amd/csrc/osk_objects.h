@@ -148,6 +148,10 @@ struct osk_seg {
     int sq6_probes = 0;                // (guarded by mu)
     int64_t sq6_probe_rows = 0, sq6_probe_rebound = 0;
     int units8 = 0;
+    // nested k-NN (osk_seg_set_parents, once per segment): each row's parent rank among the leaf's parent
+    // docs ([L] the BitSetProducer of the nested path), and their number; guarded by mu
+    int32_t* d_row_parent = nullptr;
+    int64_t n_parents = 0;
     std::mutex mu;
     std::atomic<int> refs{1};          // the reader's reference + one per view that groups the segment
     osk_view* self_view = nullptr;     // single-segment view behind osk_seg_search (holds no reference)
@@ -228,6 +232,14 @@ struct osk_view {
     int64_t max_tile_rows = 0;             // the largest tile's rows (sizes the mask: thr_words_per_wave)
     osk::DevBuf ws_thr_mask, ws_thr_wcounts, ws_thr_offsets, ws_thr_min, ws_thr_out;
     int64_t thr_calls = 0;
+    // nested k-NN (osk_nested.hip), built at the first nested search or by osk_view_warm (ensure_nested): each
+    // segment's row→parent table and parent-slot base (a shard's parent slots are contiguous), the parent
+    // tiles and their shard ranges; the per-pass best-child keys and the parent tiles' candidates
+    bool nest_ready = false;
+    int64_t nest_parents = 0;
+    int n_ptiles = 0;
+    osk::DevBuf d_nest_segs, d_ptiles, d_shard_ptile_begin, ws_nest_best, ws_nest_cand;
+    int64_t nest_calls = 0;
     bool gather_ready = false;
     int n_gtiles = 0, n_gslices = 0;
     osk::DevBuf d_gtiles, d_gslices, d_gshard_slice_begin, d_seg_tiles;
@@ -301,4 +313,8 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k, co
 int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const float* d_min_scores,
                               const uint64_t* const* d_accept, int cap, int32_t* d_docs, float* d_scores,
                               int32_t* d_count, int64_t* d_total, int64_t* d_visited, hipStream_t st);
+// Per-shard nested k-NN on the device: the k best parents, each by its best child (caller holds v->mu;
+// device current).  Same key layout as view_search_device.
+int32_t view_nested_device(osk_view* v, const void* d_queries, int nq, int k, const uint64_t* const* d_accept,
+                           uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st);
 }  // namespace osk

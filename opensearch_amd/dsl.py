@@ -13,6 +13,9 @@ plugin's public request format so existing requests keep working:
   query    {"knn": {"<field>": {"vector": [...], "k": 10, "filter": <query>}}}
            {"knn": {"<field>": {"vector": [...], "min_score": 0.8, "filter": <query>}}}   (radial search:
            every document scoring at least min_score; exactly one of k / min_score)
+           {"nested": {"path": "<path>", "query": {"knn": {...}}, "score_mode": "max"}}   (nested k-NN: k distinct
+           parent documents, each by its best child; the inner builder then returns [L]
+           DiversifyingChildrenFloat/ByteKnnVectorQuery — NestedQueryBuilder below)
 
 `KnnQueryBuilder.do_to_query` ([L] AbstractQueryBuilder.doToQuery, S/index/query/AbstractQueryBuilder.java:
 155) returns Lucene's own `KnnFloatVectorQuery` / `KnnByteVectorQuery` (opensearch_amd.lucene), whose
@@ -33,8 +36,9 @@ from typing import Any, Callable
 
 import numpy as np
 
-from .lucene import (ByteVectorSimilarityQuery, FloatVectorSimilarityQuery, KnnByteVectorQuery, KnnFloatVectorQuery,
-                     VectorEncoding, VectorSimilarityFunction)
+from .lucene import (ByteVectorSimilarityQuery, DiversifyingChildrenByteKnnVectorQuery,
+                     DiversifyingChildrenFloatKnnVectorQuery, FloatVectorSimilarityQuery, KnnByteVectorQuery,
+                     KnnFloatVectorQuery, VectorEncoding, VectorSimilarityFunction)
 
 MAX_RESULT_WINDOW = 10000          # index.max_result_window default, S/index/IndexSettings.java:223-226
 MAX_DIMENSION = 4096               # libosknn's OSK_MAX_DIM
@@ -130,6 +134,11 @@ class QueryShardContext:
     (S/index/query/QueryShardContext.java:104; bitsetFilter :369)."""
     mappings: dict[str, Any]                                   # field → KnnVectorFieldType or "keyword"/"long"
     doc_values: Callable[[Any, str], np.ndarray] | None = None  # (leaf, field) → values per doc of the leaf
+    # nested documents: (leaf, path) → bool[max_doc], the docs that are parents of `path`'s nested children
+    # (the BitSetProducer of the path's parent filter, QueryShardContext.bitsetFilter)
+    parent_docs: Callable[[Any, str], np.ndarray] | None = None
+    # set by an enclosing `nested` query for its inner query (QueryShardContext.getParentFilter): leaf → bool[max_doc]
+    parent_filter: Callable | None = None
 
     def field_type(self, name: str):
         if name not in self.mappings:
@@ -314,6 +323,15 @@ class KnnQueryBuilder:
             if ctx.doc_values is None:
                 raise QueryShardException("[knn] filter needs the shard's doc values")
             filt = lambda leaf, q=self.filter: _eval_filter(q, ctx, leaf)   # noqa: E731
+        if ctx.parent_filter is not None:
+            # inside `nested`: [L] DiversifyingChildrenFloat/ByteKnnVectorQuery(field, target, childFilter, k,
+            # parentsFilter) — k distinct parents, each by its best child (what the k-NN plugin builds when
+            # QueryShardContext.getParentFilter() is set)
+            if self.min_score is not None:
+                raise QueryShardException("[knn] min_score is not supported inside a [nested] query")
+            cls = (DiversifyingChildrenByteKnnVectorQuery if ft.encoding == VectorEncoding.BYTE
+                   else DiversifyingChildrenFloatKnnVectorQuery)
+            return cls(self.field_name, target, filt, self.k, ctx.parent_filter)
         if self.min_score is not None:
             # [L] Float/ByteVectorSimilarityQuery(field, target, traversalSimilarity, resultSimilarity, filter):
             # a flat field has no graph to traverse, so both similarities are min_score
@@ -326,3 +344,68 @@ class KnnQueryBuilder:
 def parse_query(body: dict | str) -> KnnQueryBuilder:
     """SearchModule's registered parser for the `knn` NamedWriteable (S/search/SearchModule.java:1255-1258)."""
     return KnnQueryBuilder.from_xcontent(body)
+
+
+# ------------------------------------------------------------------------------------------------
+# the nested query builder (S/index/query/NestedQueryBuilder.java) around a knn query
+# ------------------------------------------------------------------------------------------------
+NESTED_NAME = "nested"
+SCORE_MODES = ("max", "avg", "sum", "min", "none")
+
+
+@dataclass
+class NestedQueryBuilder:
+    """`{"nested": {"path": …, "query": {"knn": …}, "score_mode": …}}`.  A nested k-NN query returns each parent
+    once, through its best child, so every score_mode but "none" gives the child's score; only "max" (the
+    k-NN plugin's documented mode for nested fields) is served."""
+    path: str
+    query: KnnQueryBuilder
+    score_mode: str = "max"
+
+    def __post_init__(self):
+        if not self.path or not isinstance(self.path, str):
+            raise ValueError("[nested] requires 'path' field")
+        if not isinstance(self.query, KnnQueryBuilder):
+            raise ValueError("[nested] requires a [knn] 'query'")
+        if self.score_mode not in SCORE_MODES:
+            raise ValueError(f"[nested] illegal score_mode [{self.score_mode}]")
+        if self.score_mode != "max":
+            raise ValueError("[nested] around [knn] serves score_mode [max] only")
+
+    def to_xcontent(self) -> dict:
+        return {NESTED_NAME: {"path": self.path, "query": self.query.to_xcontent(), "score_mode": self.score_mode}}
+
+    @classmethod
+    def from_xcontent(cls, body: dict | str) -> "NestedQueryBuilder":
+        if isinstance(body, str):
+            body = json.loads(body)
+        if not isinstance(body, dict) or set(body) != {NESTED_NAME}:
+            raise ParsingException("expected a [nested] query")
+        inner = body[NESTED_NAME]
+        if not isinstance(inner, dict):
+            raise ParsingException("[nested] body must be an object")
+        unknown = set(inner) - {"path", "query", "score_mode"}
+        if unknown:
+            raise ParsingException(f"[nested] unknown field(s) {sorted(unknown)}")
+        if "path" not in inner or "query" not in inner:
+            raise ParsingException("[nested] requires [path] and [query]")
+        try:
+            return cls(inner["path"], KnnQueryBuilder.from_xcontent(inner["query"]), inner.get("score_mode", "max"))
+        except ParsingException:
+            raise
+        except ValueError as e:
+            raise ParsingException(str(e)) from e
+
+    def do_to_query(self, ctx: QueryShardContext):
+        """NestedQueryBuilder.doToQuery: the inner query is built with the path's parent filter set on the
+        context; the join to parents ([L] ToParentBlockJoinQuery) is lucene.shard_nested_query_phase."""
+        if ctx.parent_docs is None:
+            raise QueryShardException(f"[nested] failed to find nested object under path [{self.path}]")
+        inner_ctx = QueryShardContext(ctx.mappings, ctx.doc_values, ctx.parent_docs,
+                                      lambda leaf, path=self.path: ctx.parent_docs(leaf, path))
+        return self.query.do_to_query(inner_ctx)
+
+
+def parse_nested_query(body: dict | str) -> NestedQueryBuilder:
+    """SearchModule's parser entry for `nested` (around a `knn` query)."""
+    return NestedQueryBuilder.from_xcontent(body)

@@ -233,6 +233,39 @@ class GpuFlatVectorsReader:
                                              ptr(count), ptr(total), ptr(visited)))
         return docs, scores, count, total, visited
 
+    def set_parents(self, parent_mask) -> None:
+        """Register the leaf's parent docs ([L] the nested path's BitSetProducer, cached per segment):
+        parent_mask is bool[max_doc].  Once per segment — the same mask again is a no-op, another one raises."""
+        mask = np.ascontiguousarray(np.asarray(parent_mask, dtype=bool))
+        if len(mask) != self.max_doc:
+            raise ValueError(f"parent mask has {len(mask)} docs, the leaf {self.max_doc}")
+        have = getattr(self, "parent_mask", None)
+        if have is not None:
+            if not np.array_equal(have, mask):
+                raise ValueError("a different parent set is already registered on this segment")
+            return
+        check(lib().osk_seg_set_parents(self.handle, ptr(bits_from_bool(mask))))
+        self.parent_mask = mask.copy()
+
+    def n_parents(self) -> int:
+        n = C.c_int64()
+        check(lib().osk_seg_parents(self.handle, C.byref(n)))
+        return n.value
+
+    def search_nested(self, targets, k: int, accept_bits: np.ndarray | None = None):
+        """Nested k-NN (osk_seg_search_nested): the k best parents, each by its best accepted child — child docs
+        and their scores in search_batch's layout: (scores[nq,k], docs[nq,k], counts[nq], visited[nq])."""
+        q = _as_query_array(targets, self.encoding, self.dim)
+        nq = q.shape[0]
+        scores = np.empty((nq, k), np.float32)
+        docs = np.empty((nq, k), np.int32)
+        counts = np.empty(nq, np.int32)
+        visited = np.empty(nq, np.int64)
+        ab = None if accept_bits is None else np.ascontiguousarray(accept_bits, dtype=np.uint64)
+        check(lib().osk_seg_search_nested(self.handle, ptr(q), nq, k, ptr(ab), ptr(scores), ptr(docs),
+                                          ptr(counts), ptr(visited)))
+        return scores, docs, counts, visited
+
     def search(self, field: str, target, k: int, accept_docs: np.ndarray | None = None) -> TopDocs:
         """[L] KnnVectorsReader.search(field, target, KnnCollector(k), AcceptDocs) → the collector's
         topDocs(): segment-local docs, score desc / doc asc, totalHits = visited (EQUAL_TO)."""
@@ -513,6 +546,109 @@ class GpuByteVectorSimilarityQuery(_GpuVectorSimilarityQuery):
     encoding = VectorEncoding.BYTE
 
 
+# ------------------------------------------------------------------------------------------------
+# [L] DiversifyingChildren{Float,Byte}KnnVectorQuery: nested k-NN — k distinct parents, each by its best child
+# ------------------------------------------------------------------------------------------------
+class _DiversifyingChildrenKnnVectorQuery(_KnnVectorQuery):
+    """[L] DiversifyingChildrenFloatKnnVectorQuery(field, target, childFilter, k, parentsFilter) on a flat
+    field (its exactSearch): the accepted children (liveDocs ∩ childFilter) are scored, each parent —
+    nextSetBit(child) in the leaf's parent bitset — keeps its best child (highest score, then lowest doc), and
+    the k best parents come back as their best CHILD docs.  `parents_filter(leaf)` returns bool[max_doc]
+    ([L] BitSetProducer.getBitSet(context)); it is registered on the leaf's reader at first use.
+
+    `rewrite` takes Lucene's per-leaf route: one reader call per leaf, docBase added, TopDocs.merge(k)."""
+
+    def __init__(self, field: str, target, child_filter, k: int, parents_filter):
+        super().__init__(field, target, k, child_filter)
+        if parents_filter is None:
+            raise ValueError("parentsFilter is required")
+        self.parents_filter = parents_filter
+
+    def _register(self, leaf: LeafReaderContext) -> None:
+        leaf.reader.set_parents(self.parents_filter(leaf))
+
+    def rewrite(self, leaves: Iterable[LeafReaderContext]) -> TopDocs:
+        per_leaf = []
+        for leaf in leaves:
+            if leaf.reader.field != self.field:
+                continue
+            self._register(leaf)
+            acc = self._accept(leaf)
+            s, d, c, v = leaf.reader.search_nested(self.target, self.k, None if acc is None else bits_from_bool(acc))
+            hits = [ScoreDoc(int(d[0, i]) + leaf.doc_base, float(s[0, i])) for i in range(int(c[0]))]
+            per_leaf.append(TopDocs(TotalHits(int(v[0])), hits))
+        if not per_leaf:
+            return TopDocs(TotalHits(0), [])
+        return TopDocs.merge(0, self.k, per_leaf)
+
+
+class DiversifyingChildrenFloatKnnVectorQuery(_DiversifyingChildrenKnnVectorQuery):
+    """[L] DiversifyingChildrenFloatKnnVectorQuery(field, float[] query, childFilter, k, parentsFilter)."""
+    encoding = VectorEncoding.FLOAT32
+
+
+class DiversifyingChildrenByteKnnVectorQuery(_DiversifyingChildrenKnnVectorQuery):
+    """[L] DiversifyingChildrenByteKnnVectorQuery(field, byte[] query, childFilter, k, parentsFilter)."""
+    encoding = VectorEncoding.BYTE
+
+
+class _GpuDiversifyingChildrenKnnVectorQuery(_DiversifyingChildrenKnnVectorQuery):
+    """The plugin's nested query: ONE osk_view_search_nested call per shard over the cached view of all its
+    leaves (_GpuKnnVectorQuery's cache and reader-closed eviction).  Same result as the per-leaf route."""
+
+    def rewrite(self, leaves: Iterable[LeafReaderContext]) -> TopDocs:
+        leaves = [lf for lf in leaves if lf.reader.field == self.field]
+        if not leaves:
+            return TopDocs(TotalHits(0), [])
+        for lf in leaves:
+            self._register(lf)
+        G = _GpuKnnVectorQuery
+        e = G._acquire_view(self, leaves)
+        try:
+            accept = [self._accept(lf) for lf in leaves]
+            if all(a is None for a in accept):
+                accept = None
+            s, d, _, c, _, _ = e.view.search_nested(self.target, self.k, 0, self.k, accept=accept)
+        finally:
+            G._release_view(e)
+        n = int(c[0])
+        return TopDocs(TotalHits(n), [ScoreDoc(int(d[0, i]), float(s[0, i])) for i in range(n)])
+
+
+class GpuDiversifyingChildrenFloatKnnVectorQuery(_GpuDiversifyingChildrenKnnVectorQuery):
+    encoding = VectorEncoding.FLOAT32
+
+
+class GpuDiversifyingChildrenByteKnnVectorQuery(_GpuDiversifyingChildrenKnnVectorQuery):
+    encoding = VectorEncoding.BYTE
+
+
+@dataclass
+class NestedHit(ScoreDoc):
+    """A parent hit of a nested query: doc = the parent, score = the best child's (score_mode max), and the
+    child doc that produced it (the inner hit)."""
+    child_doc: int = -1
+
+
+def shard_nested_query_phase(query: _DiversifyingChildrenKnnVectorQuery, leaves: Sequence[LeafReaderContext],
+                             parents_filter, from_: int, size: int) -> TopDocs:
+    """The shard's query phase for `nested { knn }`: the diversifying query's k child hits, each joined to its
+    parent ([L] ToParentBlockJoinQuery: the parent of child c is nextSetBit(c) in the leaf's parent bitset) and
+    scored by that child (score_mode max — each parent has exactly one child among the hits), then the shard
+    collector: score desc, parent doc asc, cut to from+size.  totalHits = the parents matched."""
+    rewritten = query.rewrite(leaves)
+    ordered = sorted((lf for lf in leaves if lf.reader.field == query.field), key=lambda lf: lf.doc_base)
+    tables = [(lf, np.flatnonzero(np.asarray(parents_filter(lf), dtype=bool))) for lf in ordered]
+    hits = []
+    for h in rewritten.score_docs:
+        lf, pdocs = [(lf, p) for lf, p in tables if lf.doc_base <= h.doc < lf.doc_base + lf.max_doc][-1]
+        local = h.doc - lf.doc_base
+        parent = int(pdocs[np.searchsorted(pdocs, local, side="left")])
+        hits.append(NestedHit(parent + lf.doc_base, h.score, h.shard_index, h.doc))
+    hits.sort(key=lambda x: (-x.score, x.doc))
+    return TopDocs(TotalHits(len(hits)), hits[: from_ + size])
+
+
 def shard_similarity_query_phase(query: _VectorSimilarityQuery, leaves: Sequence[LeafReaderContext], from_: int,
                                  size: int) -> TopDocs:
     """The shard's query phase for a similarity query: a TopScoreDocCollector over the query's scorer with
@@ -609,6 +745,24 @@ class DeviceShardSet:
                 ptrs.append(b.ctypes.data)
         return (C.c_void_p * len(ptrs))(*ptrs)
 
+    def search_nested(self, targets, k: int, from_: int = 0, size: int = 10, accept=None):
+        """Nested k-NN per shard (the k best parents, each by its best child) + coordinator merge —
+        osk_view_search_nested; `search`'s outputs, docs = shard-local child docs.  Every leaf's reader needs
+        its parents registered (GpuFlatVectorsReader.set_parents)."""
+        q = _as_query_array(targets, self.encoding, self.dim)
+        nq = q.shape[0]
+        scores = np.empty((nq, size), np.float32)
+        docs = np.empty((nq, size), np.int32)
+        shard = np.empty((nq, size), np.int32)
+        count = np.empty(nq, np.int32)
+        total = np.empty(nq, np.int64)
+        mx = np.empty(nq, np.float32)
+        keep: list = []
+        acc_arr = self._accept_table(accept, keep)
+        check(lib().osk_view_search_nested(self.handle, ptr(q), nq, k, from_, size, acc_arr, ptr(scores),
+                                           ptr(docs), ptr(shard), ptr(count), ptr(total), ptr(mx)))
+        return scores, docs, shard, count, total, mx
+
     def search_threshold(self, targets, min_score, accept=None, cap: int = 1024):
         """Every accepted vector of each shard scoring ≥ min_score (one per target, or a scalar), shard-local
         docs ascending: (docs[nq,S,cap], scores[nq,S,cap], count[nq,S], total[nq,S]) — osk_view_search_threshold.
@@ -634,7 +788,7 @@ class DeviceShardSet:
 
     def counter(self, name: str) -> int:
         """A named counter of the view (osk_view_counter): "sq8_calls", "sq8_fallback_queries",
-        "sq8_rescored_rows", "mfma_calls", "mfma_fallback_queries", "threshold_calls"."""
+        "sq8_rescored_rows", "mfma_calls", "mfma_fallback_queries", "threshold_calls", "nested_calls"."""
         v = C.c_int64()
         check(lib().osk_view_counter(self.handle, name.encode(), C.byref(v)))
         return v.value
