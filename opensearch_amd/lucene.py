@@ -244,7 +244,8 @@ class GpuFlatVectorsReader:
             if not np.array_equal(have, mask):
                 raise ValueError("a different parent set is already registered on this segment")
             return
-        check(lib().osk_seg_set_parents(self.handle, ptr(bits_from_bool(mask))))
+        bits = bits_from_bool(mask)   # a name keeps the words alive while the call reads them: ptr() is an address only
+        check(lib().osk_seg_set_parents(self.handle, ptr(bits)))
         self.parent_mask = mask.copy()
 
     def n_parents(self) -> int:

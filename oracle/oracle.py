@@ -112,7 +112,8 @@ def synth_par(row0: int, n: int, dim: int, seed: int, dist: int, nthreads: int =
 
 def score(q: np.ndarray, x: np.ndarray, sim: int, order: int = ORDER_DEVICE) -> float:
     if q.dtype == np.int8:
-        return float(lib().orc_score_i8(_p(np.ascontiguousarray(q)), _p(np.ascontiguousarray(x)), len(q), sim))
+        q, x = np.ascontiguousarray(q), np.ascontiguousarray(x, np.int8)   # named: _p() is an address only
+        return float(lib().orc_score_i8(_p(q), _p(x), len(q), sim))
     q = np.ascontiguousarray(q, np.float32)
     x = np.ascontiguousarray(x, np.float32)
     return float(lib().orc_score_f32(_p(q), _p(x), len(q), sim, order))

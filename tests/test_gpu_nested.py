@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from opensearch_amd import _lib, dsl as Q, lucene as LU
+from oracle import byte_reference as BR
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -100,6 +101,12 @@ def nested_reader(rows, sim, enc, o2d, parents, max_doc):
 # ------------------------------------------------------------------------------------------------
 CASES = [(F32, dim, sim) for dim in (3, 96, 128, 768, 1030) for sim in SIM] + \
         [(BYTE, dim, sim) for dim in (16, 100, 768) for sim in (SIM.EUCLIDEAN, SIM.DOT_PRODUCT)]
+# byte lane configs whose 8-query instantiation reads its query fragments from LDS (dims above 256), and 250 which
+# keeps them in registers, on the two similarities the cases above leave out; these corpora carry the byte edge
+# set (byte_reference.edge_rows: a zero child — NaN under COSINE — among them) and the queries all −128, all 127
+# and all 0
+BYTE_EDGE_CASES = [(BYTE, dim, sim) for dim in (250, 1100, 3000, 4096) for sim in (SIM.COSINE, SIM.MAXIMUM_INNER_PRODUCT)]
+CASES += BYTE_EDGE_CASES
 
 
 @pytest.mark.parametrize("enc,dim,sim", CASES, ids=lambda v: getattr(v, "name", str(v)))
@@ -107,6 +114,10 @@ def test_lane_configs(enc, dim, sim):
     n = 4097
     rows = synth(n, dim, 100 + dim, enc)
     qs = synth(9, dim, 7 + dim, enc)
+    edges = (enc, dim, sim) in BYTE_EDGE_CASES
+    if edges:
+        BR.inject_edges(rows)
+        BR.edge_queries(qs)          # 0: all −128, 1: all 127, 4: all 0, 8 (the second pass's only query): alternating
     o2d, parents, max_doc = families(n, 11)
     assert {int(f) for f in np.diff(np.concatenate([[-1], parents])) - 1} >= {1, 17, 65, 300}
     r = nested_reader(rows, sim, enc, o2d, parents, max_doc)
@@ -119,10 +130,29 @@ def test_lane_configs(enc, dim, sim):
                 assert_result((s[i], d[i], c[i]), nested_reference(scored[i][0], scored[i][1], parents, k), k,
                               (enc, dim, sim, k, i))
                 assert v[i] == scored[i][2] == n
-            assert c[0] == min(k, len(parents))
+            if edges:     # (a family whose only child is a zero vector is absent under COSINE)
+                assert c[0] == min(k, len(np.unique(np.searchsorted(parents, scored[0][0], side="left"))))
+            else:
+                assert c[0] == min(k, len(parents))
             s1, d1, c1, v1 = r.search_nested(qs[3], k)
             assert_result((s1[0], d1[0], c1[0]), nested_reference(scored[3][0], scored[3][1], parents, k), k)
             assert v1[0] == n
+            if edges:
+                # one 8-query call: a single pass of the 8-query instantiation
+                s8, d8, c8, v8 = r.search_nested(qs[:8], k)
+                for i in range(8):
+                    assert_result((s8[i], d8[i], c8[i]), nested_reference(scored[i][0], scored[i][1], parents, k), k,
+                                  ("8-query", dim, sim, k, i))
+                    assert v8[i] == n
+                assert c[4] == (0 if sim == SIM.COSINE else min(k, len(parents)))     # the zero query
+        if edges:
+            # the oracle's scores are byte_reference's, row for row (COSINE: the zero children are the ones left out)
+            for i in (0, 1, 3, 8):
+                ref = BR.scores(rows, qs[i], int(sim))
+                order = np.argsort(scored[i][0], kind="stable")
+                assert np.array_equal(o2d[~np.isnan(ref)], scored[i][0][order])
+                assert np.array_equal(ref[~np.isnan(ref)].view(np.uint32), scored[i][1][order].view(np.uint32))
+                assert (len(scored[i][0]) < n) == (sim == SIM.COSINE)
     finally:
         r.close()
 

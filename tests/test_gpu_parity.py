@@ -74,11 +74,12 @@ def test_i8_exact(dim, sim):
 
 
 @pytest.mark.parametrize("stream", [1, 0], ids=["i8_stream", "scan_i8"])
-@pytest.mark.parametrize("dim", [1, 15, 64, 96, 100, 257, 512, 768, 1000, 2048, 4096])
+@pytest.mark.parametrize("dim", [1, 15, 64, 96, 100, 250, 257, 512, 768, 1000, 2048, 4096])
 @pytest.mark.parametrize("sim", SIMS, ids=lambda s: s.name)
 def test_i8_single_query_stream(dim, sim, stream):
     """One byte query per search, no filter: scan_i8_stream (exact-width lanes, 4 row groups in flight)
-    and scan_i8 both equal the oracle; ragged row counts leave partial row groups at wave ends."""
+    and scan_i8 both equal the oracle; ragged row counts leave partial row groups at wave ends.  The dims
+    take every one of scan_i8_stream's 8 configs (250: 9–16 units)."""
     rows = corpus(3000 + dim % 13, dim, sim, 23, I8)
     queries = corpus(3, dim, sim, 24, I8)
     r = LU.GpuFlatVectorsReader("v", rows, sim, I8)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from opensearch_amd import _lib, dsl as Q, lucene as LU
+from oracle import byte_reference as BR
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +75,11 @@ def thresholds(scored):
 # ------------------------------------------------------------------------------------------------
 CASES = [(F32, dim, sim) for dim in (3, 96, 128, 768, 1030) for sim in SIM] + \
         [(BYTE, dim, sim) for dim in (16, 100, 768) for sim in (SIM.EUCLIDEAN, SIM.DOT_PRODUCT)]
+# byte lane configs whose 4-query instantiation reads its query fragments from LDS (dims above 1024) or keeps them
+# in registers (250), on the two similarities the cases above leave out; these corpora carry the byte edge set
+# (byte_reference.edge_rows: all −128, all 127, alternating, all 0 — NaN under COSINE —, a duplicate, all 1)
+BYTE_EDGE_CASES = [(BYTE, dim, sim) for dim in (250, 1100, 3000, 4096) for sim in (SIM.COSINE, SIM.MAXIMUM_INNER_PRODUCT)]
+CASES += BYTE_EDGE_CASES
 
 
 @pytest.mark.parametrize("enc,dim,sim", CASES, ids=lambda v: getattr(v, "name", str(v)))
@@ -81,6 +87,9 @@ def test_lane_configs_and_thresholds(enc, dim, sim):
     n = 4097
     rows = synth(n, dim, 100 + dim, enc)
     q = synth(2, dim, 7 + dim, enc)[1]
+    edges = (enc, dim, sim) in BYTE_EDGE_CASES
+    if edges:
+        BR.inject_edges(rows)
     r = LU.GpuFlatVectorsReader("v", rows, sim, enc)
     try:
         scored = all_scores(("lane", enc, dim, sim), rows, q, sim)
@@ -99,6 +108,23 @@ def test_lane_configs_and_thresholds(enc, dim, sim):
         d1, s1, c1, t1, v1 = r.search_threshold(q, ms[1], None, cap)
         assert_hits((d1[0], s1[0], c1[0], t1[0]), reference(scored, ms[1]), cap)
         assert v1[0] == n
+        if edges:
+            # the oracle's scores are byte_reference's, row for row (the zero rows are the ones left out)
+            ref = BR.scores(rows, q, int(sim))
+            assert np.array_equal(np.flatnonzero(~np.isnan(ref)), scored[0])
+            assert np.array_equal(ref[scored[0]].view(np.uint32), scored[1].view(np.uint32))
+            assert (len(scored[0]) < n) == (sim == SIM.COSINE)
+            # the edge queries: all −128, all 127, and all 0 (COSINE: every score NaN, no hit; MIP: every score 1)
+            for j, fill in enumerate((-128, 127, 0)):
+                qe = np.full(dim, fill, np.int8)
+                se = all_scores(("lane-edge", dim, sim, j), rows, qe, sim)
+                me = np.array([NEG_INF, jth_best(se, 10) if len(se[1]) else 0.0, 1.0, 0.5], np.float32)
+                d, s, c, t, v = r.search_threshold(np.repeat(qe[None], len(me), 0), me, None, cap)
+                for i, m in enumerate(me):
+                    assert_hits((d[i], s[i], c[i], t[i]), reference(se, m), cap, (dim, sim, fill, m))
+                    assert v[i] == n
+                if fill == 0:
+                    assert t[0] == (0 if sim == SIM.COSINE else n) and t[2] == t[0]
     finally:
         r.close()
 

@@ -177,3 +177,42 @@ def test_numpy_reference_matches_the_lucene_loop(seed):
         shuffle = rng.permutation(int(keep.sum()))                   # the reference must not depend on row order
         gd, gs = N.nested_reference(o2d[keep][shuffle], scores[keep][shuffle], parents, k)
         assert np.array_equal(gd, wd) and np.array_equal(gs.view(np.uint32), ws.view(np.uint32)), (seed, k)
+
+
+def test_set_parents_keeps_the_bitset_alive_while_the_library_reads_it(monkeypatch):
+    """`_lib.ptr` is an address only: the packed parent words must have an owner for the length of the
+    osk_seg_set_parents call.  (They were a temporary once, freed before the call: the allocator's free-list
+    words then stood in for the parent bits of docs 0–127, and rows there were credited to other families, so
+    tests/test_gpu_nested.py::test_view_batch_and_filter gave a wrong hit now and then.)"""
+    import weakref
+    from opensearch_amd import lucene as LU
+
+    class Tracked(np.ndarray):
+        pass
+
+    state = {}
+    real_bits = LU.bits_from_bool
+
+    def tracked_bits(mask):
+        a = real_bits(mask).view(Tracked)        # (the view owns a reference to the packed words)
+        state["ref"] = weakref.ref(a)
+        return a
+
+    class FakeLib:
+        def osk_seg_set_parents(self, handle, addr):
+            owner = state["ref"]()
+            assert owner is not None, "the parent words were freed before the library read them"
+            assert addr == owner.ctypes.data
+            state["seen"] = np.array(owner, np.uint64)
+            return _lib.OSK_OK
+
+    monkeypatch.setattr(LU, "bits_from_bool", tracked_bits)
+    monkeypatch.setattr(LU, "lib", lambda: FakeLib())
+    r = LU.GpuFlatVectorsReader("v", None, LU.VectorSimilarityFunction.EUCLIDEAN, max_doc=200, _handle=1, _dim=4, _n=150)
+    try:
+        mask = np.arange(200) % 5 == 4
+        r.set_parents(mask)
+        assert np.array_equal(state["seen"], real_bits(mask))
+        assert np.array_equal(r.parent_mask, mask)
+    finally:
+        r._h = C.c_void_p(None)                   # (no segment behind the handle: nothing to release)
