@@ -306,7 +306,10 @@ int32_t osk_view_stats(osk_view* view, int64_t* batched_calls, int64_t* fallback
 int32_t osk_view_counter(osk_view* view, const char* name, int64_t* value);
 /* Testing build only (the shipped library returns OSK_ERR_UNSUPPORTED): copy `bytes` of an internal
  * buffer of the view's last search ("akeys", "cand_a", "flags", "qsplit", "qnorm", "sq8cand", "sq8lb",
- * "qc", "settle_trace") to host memory. */
+ * "qc", "settle_trace") to host memory.  "sel_lb" / "sel_ub": the select path's certified score bounds of
+ * the last query searched with k > 12, one sortable u32 per view row (segment s's row r at the rows of the
+ * segments before it + r; 0 = no record).  "sq8_lists": one int64, the wave lists per query of the last
+ * prefiltered search ("sq8cand" / "sq8lb" are [queries][lists][16]). */
 int32_t osk_view_debug_copy(osk_view* view, const char* name, void* host, int64_t bytes);
 
 /* Device time of this thread's last synchronous host search (osk_seg_search / osk_view_search), for a

@@ -1207,8 +1207,12 @@ int32_t ensure_sq8_seg(osk_seg* s, hipStream_t st) {
         set_error(std::string("hipMalloc of the prefilter bound terms failed: ") + hipGetErrorString(e));
         return OSK_ERR_OOM;
     }
+    // (the kernel also reports whether some row lies outside the certificate's range: one int, read below)
+    int* d_oor = nullptr;
+    OSK_HIP(hipMalloc(reinterpret_cast<void**>(&d_oor), sizeof(int)));
+    OSK_HIP(hipMemsetAsync(d_oor, 0, sizeof(int), st));
     OSK_HIP(launch_sq8_quantize(static_cast<const float4*>(s->d_rows), s->n_rows, s->units, s->units, u8, q8, aux,
-                                0, st));
+                                0, st, d_oor));
     // the 6-bit tier of single queries, where the dim has one and the tier is on (a node
     // that sets tune sq6 = 0 before staging never holds the copy; calibration frees it per segment)
     void* q6 = nullptr;
@@ -1230,6 +1234,10 @@ int32_t ensure_sq8_seg(osk_seg* s, hipStream_t st) {
         OSK_HIP(launch_sq6_quantize(static_cast<const float4*>(s->d_rows), s->n_rows, s->units, s->dim, q6, aux6, st));
     }
     OSK_HIP(hipStreamSynchronize(st));
+    int oor = 0;
+    OSK_HIP(hipMemcpy(&oor, d_oor, sizeof(int), hipMemcpyDeviceToHost));
+    (void)hipFree(d_oor);
+    s->sq8_out_of_range = oor != 0;
     s->d_q8 = q8;
     s->d_q8aux = aux;
     s->d_q6 = q6;
@@ -1519,6 +1527,8 @@ int32_t ensure_sq8(osk_view* v, hipStream_t st) {
     }
     OSK_HIP(hipStreamSynchronize(st));
     v->sq6_ready = all6;
+    v->sq8_range_ok = true;
+    for (const osk_seg* sg : v->segs) v->sq8_range_ok = v->sq8_range_ok && !sg->sq8_out_of_range;
     v->sq8_ready = true;
     return OSK_OK;
 }
@@ -1733,6 +1743,7 @@ int32_t sq8_search(osk_view* v, const void* d_queries, int nq, int k, int UP, co
     p.visited = reinterpret_cast<unsigned long long*>(d_visited);
     p.n_tiles = n_scan_tiles;
     p.n_lists = 4 * n_scan_tiles;
+    v->sq8_lists_last = p.n_lists;
     p.units8 = u8;
     p.sim = v->sim;
     p.gam = v->sq8_gam;
@@ -2045,6 +2056,7 @@ int32_t select_search(osk_view* v, const void* d_queries, int nq, int k, int UP,
         p.qnorm = v->ws_qnorm.as<float>() + q;
         p.q8 = v->ws_q8.as<int4>() + (size_t)q * u8;
         p.qc = v->ws_qc.as<float4>() + q;
+        p.qflags = bounds ? v->ws_flags.as<int>() + q : nullptr;
         p.out_keys = d_shard_keys + (size_t)q * S * k;
         p.out_counts = d_shard_counts + (size_t)q * S;
         p.visited = q == 0 ? reinterpret_cast<unsigned long long*>(d_visited) : nullptr;
@@ -2157,8 +2169,9 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
     //     fitted to those three, profiles/r02q/c2_batches_*.jsonl, c3_batches_*.jsonl).
     // 96-dim rows stay on the prefilter at any batch, 768-dim rows move to bf16×3 blocks from about 160
     // queries, and small views (C2) from about 128.  sq8_cost_pct scales the prefilter's side (100 = the model).
-    const bool sq8_on = v->enc == ENC_FLOAT32 && g_tuning.sq8;
-    const bool sq8_ok = sq8_on && k <= kKQ - 4;
+    // A view holding a row outside the certificate's range (osk_sq8.hip sq8_in_range; known once the int8
+    // copy is built) is served by the exact paths, as if the prefilter were off.
+    bool sq8_on = v->enc == ENC_FLOAT32 && g_tuning.sq8 && !(v->sq8_ready && !v->sq8_range_ok);
     double R = 0.0;
     for (const osk_seg* sg : v->segs) R += (double)sg->n_rows;
     const int u8v = (v->dim + 15) / 16;
@@ -2167,13 +2180,26 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
     const double bf_us = (double)((nq + 255) / 256) * (R * (0.153 + 0.00119 * v->dim) * 1e-3 + 325.0);
     const bool blocks_cheaper = bf_us * 100.0 <= sq8_us * (double)g_tuning.sq8_cost_pct &&
                                 !(g_tuning.sq8_wide_force && sq8_wide_pick(v, nq, d_accept != nullptr));
-    const bool batched = v->enc == ENC_FLOAT32 && g_tuning.mfma_min_batch > 0 &&
-                         nq >= g_tuning.mfma_min_batch && k <= kKC - 4 && (!sq8_ok || blocks_cheaper);
-    // k ≤ kKQ − 4: a tile list holds 4 more rows than k, so it rarely overflows past the certificate
-    const bool prefilter = !batched && sq8_ok;
-    // the select path: k beyond the streaming scans' 64-lane lists, or float32 k beyond the prefilter's
-    // lists (its int8 bounds pass reads ¼ of the fp32 scan's bytes)
-    const bool select = !batched && !prefilter && (k > kScanMaxK || (sq8_on && k > kKQ - 4 && g_tuning.select_mid_k));
+    bool batched = false, prefilter = false, select = false;
+    auto choose = [&]() {
+        const bool sq8_ok = sq8_on && k <= kKQ - 4;
+        batched = v->enc == ENC_FLOAT32 && g_tuning.mfma_min_batch > 0 && nq >= g_tuning.mfma_min_batch &&
+                  k <= kKC - 4 && (!sq8_ok || blocks_cheaper);
+        // k ≤ kKQ − 4: a tile list holds 4 more rows than k, so it rarely overflows past the certificate
+        prefilter = !batched && sq8_ok;
+        // the select path: k beyond the streaming scans' 64-lane lists, or float32 k beyond the prefilter's
+        // lists (its int8 bounds pass reads ¼ of the fp32 scan's bytes)
+        select = !batched && !prefilter && (k > kScanMaxK || (sq8_on && k > kKQ - 4 && g_tuning.select_mid_k));
+    };
+    choose();
+    if (prefilter || (select && sq8_on)) {   // one-time build of the int8 copy
+        const int32_t rc8 = ensure_sq8(v, st);
+        if (rc8) return rc8;
+        if (!v->sq8_range_ok) {
+            sq8_on = false;
+            choose();
+        }
+    }
     // queries → padded unit layout (zeros past dim and for the dummy queries of the last launch); the
     // prefilter path does this inside its own fused prep launch (so does the select path's bounds mode)
     if (!prefilter && !(select && sq8_on))
@@ -2182,7 +2208,6 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
     if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
 
     int32_t rc;
-    if ((prefilter || (select && sq8_on)) && (rc = ensure_sq8(v, st)) != OSK_OK) return rc;   // one-time build
     // osk_view_profile(N): every N-th call stamps its scan launches (N = 1: every call); the event stamps cost
     // a few µs of stream time around the stamped launch, so a long timed loop samples instead of stamping all
     v->profile = v->profile_every > 0 && v->profile_tick++ % (uint64_t)v->profile_every == 0;
@@ -2558,10 +2583,16 @@ int32_t osk_view_debug_copy(osk_view* v, const char* name, void* host, int64_t b
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(v->mu);
     const std::string n(name);
+    if (n == "sq8_lists") {   // (a host value: the [queries][lists][kKQ] shape of "sq8cand" / "sq8lb")
+        OSK_REQUIRE(bytes == (int64_t)sizeof(int64_t), "sq8_lists is one int64");
+        *static_cast<int64_t*>(host) = v->sq8_lists_last;
+        return OSK_OK;
+    }
     const DevBuf* b = n == "akeys" ? &v->ws_akeys : n == "cand_a" ? &v->ws_cand_a : n == "flags" ? &v->ws_flags
                     : n == "qsplit" ? &v->ws_qsplit : n == "qnorm" ? &v->ws_qnorm
                     : n == "sq8cand" ? &v->ws_sq8cand : n == "sq8lb" ? &v->ws_sq8lb : n == "qc" ? &v->ws_qc
                     : n == "settle_trace" ? &v->ws_trace
+                    : n == "sel_lb" ? &v->ws_sel_lb : n == "sel_ub" ? &v->ws_sel_ub
                     : nullptr;
     OSK_REQUIRE(b != nullptr, "unknown buffer");
     OSK_REQUIRE((size_t)bytes <= b->cap, "bytes exceed the buffer");

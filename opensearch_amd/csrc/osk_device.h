@@ -16,6 +16,20 @@ __device__ __forceinline__ float f32_round_up(double d) {   // d ≥ 0: smallest
 // ------------------------------------------------------------------------------------------------
 // bounds
 // ------------------------------------------------------------------------------------------------
+// The certificate's range.  sq8_bounds and every quick test derived from it are float expressions over the
+// bound terms {s, s·|q|, |x − s·q|, |x|²} of a row and a query; they bound the fp32 scan's value only while
+// none of their products underflows (s_x·s_b → 0 moves the centre, a product rounded to 0 drops an error
+// term) or overflows (|x|² = inf turns lo / hi into inf − inf = NaN: no record, the row is lost).  With the
+// largest |component| m of both vectors in [2^-32, 2^32] (or the vector zero) every term is ≤ 2^77 and every
+// non-zero product they form is either ≥ 2^-126 or below the 2^-20 slack by a factor ≥ 2^40 (the slack is
+// ≥ 2^-20·gam·(|x|² + |b|²) ≥ 2^-107).  Outside that range the int8 paths do not certify:
+//   * a segment with such a row reports it when its int8 copy is built (sq8_quantize), and its views are
+//     served by the exact fp32 paths;
+//   * such a query is flagged by sq8_prep (kQueryOutOfRange): the select path's writer gives every row the
+//     record [0, +inf] (every row a candidate, re-scored exactly) and the settle re-scans every list exactly.
+constexpr int kQueryOutOfRange = 2;   // bit of sq8_prep's flags[q] (bit 0: the settle's fallback mark)
+__device__ __forceinline__ bool sq8_in_range(float m) { return m == 0.0f || (m >= 0x1p-32f && m <= 0x1p32f); }
+
 // [lo, hi] ∋ the raw value the fp32 streaming scan computes for (row, query): its dot product
 // (DOT_PRODUCT / COSINE / MAXIMUM_INNER_PRODUCT) or its squared distance (EUCLIDEAN).
 //   x·b = s_x·s_b·I + e,  |e| ≤ s_x|q_x|·|δ_b| + |δ_x|·(s_b|q_b| + |δ_b|) = ax.y·qc.y + ax.z·qc.z

@@ -267,6 +267,7 @@ struct RadixState {
     int32_t pad;
 };
 struct SelParams {
+    const int* qflags;               // this query's sq8_prep flags (kQueryOutOfRange: its records are [0, +inf])
     const SegDev* segs;
     const TileDev* tiles;
     const int64_t* seg_vrow;
@@ -335,7 +336,7 @@ hipError_t launch_xhdr_fill(uint64_t* hdr, const uint64_t* w, const void* querie
                             const int32_t* shard_index, int n_shards, int sl, hipStream_t s);
 
 hipError_t launch_sq8_quantize(const float4* x, int64_t n, int units, int pitch, int units8, void* out8,
-                               float4* aux, int mode, hipStream_t s);
+                               float4* aux, int mode, hipStream_t s, int* out_of_range = nullptr);
 // ev_start / ev_stop (optional): stamped by the kernel's own dispatch packet (hipExtLaunchKernelGGL),
 // so timing a launch adds no marker packets (and no gaps) to the stream
 hipError_t launch_sq8_scan(int nq, const Sq8Params& p, hipStream_t s, hipEvent_t ev_start = nullptr,

@@ -135,6 +135,7 @@ struct osk_seg {
     // certified int8 prefilter (built at staging for float32 segments): int8 rows + per-row bound terms
     void* d_q8 = nullptr;
     float4* d_q8aux = nullptr;
+    bool sq8_out_of_range = false;   // some row lies outside the certificate's range (sq8_in_range; set with d_q8)
     void* d_q8t = nullptr;    // the int8 rows in sq8_mfma's tiled layout (osk_seg_warm / first batched prefilter)
     void* d_q8w = nullptr;        // sq8_wide's copy: codes with one scale per 16-row group, tiled (launch_sq8w_build)
     float4* d_q8auxt = nullptr;   // ...and its bound terms per 16-row group (built with d_q8t)
@@ -187,6 +188,7 @@ struct osk_view {
     osk::DevBuf d_mfma_full;               // [1] tiles whose candidate epilogue took the staging path
     // certified int8 prefilter
     bool sq8_ready = false;
+    bool sq8_range_ok = true;   // (with sq8_ready) no segment has a row outside the certificate's range
     int units8 = 0;
     float sq8_gam = 0.f, sq8_g2 = 0.f, sq8_cos_slack = 0.f;
     osk::DevBuf d_sq8_rows, d_sq8_aux, d_counters;   // counters: SettleParams::counters
@@ -221,6 +223,7 @@ struct osk_view {
     osk::DevBuf ws_pilot, ws_thr, ws_thr_counts;   // int8 MFMA prefilter: pilot keys, per-(query, shard) floors
     osk::DevBuf ws_wfloor;                          // sq8_wide: the two passes' floors [2][kWideQ][S]
     int64_t sq8_calls = 0, sq8w_calls = 0;
+    int64_t sq8_lists_last = 0;            // wave lists per query of the last prefiltered search (debug copies)
     int n_cus = 0;                         // the device's CUs (cached; the wide kernel's persistent grid)   // prefiltered searches; those whose batch took sq8_wide
     // filter pushdown by compaction (osk_filter.hip): gather tiles over the compacted accepted ordinals
     // (one round of the chip, split over segments by rows), their settle slices, per-segment tile ranges

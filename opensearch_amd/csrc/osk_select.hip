@@ -207,6 +207,8 @@ __global__ __launch_bounds__(kSelThreads) void sel_bounds(SelParams p) {
     }
     const float4 qc = p.qc[0];
     const float qnd = sim == SIM_COSINE ? p.qnorm[0] : 0.0f;
+    // a query outside the certificate's range (osk_device.h): every row's record is [0, +inf]
+    const bool qopen = (p.qflags[0] & kQueryOutOfRange) != 0;
     const int64_t vbase = p.seg_vrow[tile.seg];
     int64_t wb, we;
     wave_rows<R>(tile, wave, wb, we);
@@ -259,6 +261,10 @@ __global__ __launch_bounds__(kSelThreads) void sel_bounds(SelParams p) {
             } else {
                 ub = sim == SIM_EUCLIDEAN ? score_f32_l2(lo) : score_f32(sim, hi, qnd, xnd);
                 lb = sim == SIM_EUCLIDEAN ? score_f32_l2(hi) : score_f32(sim, lo, qnd, xnd);
+            }
+            if (qopen) {   // (wave-uniform) every score is in [0, +inf]: every row a candidate, re-scored exactly
+                lb = 0.0f;
+                ub = __builtin_inff();
             }
             nvis += __popcll(__ballot(t == 0 && valid[u]));
             // every real score is ≥ 0, whose sortable form is ≥ 2^31: 0 = no row.  A NaN bound (COSINE with a zero

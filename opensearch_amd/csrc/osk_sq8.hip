@@ -37,7 +37,8 @@ namespace osk {
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void sq8_quantize(const float4* __restrict__ X, int64_t n, int units,
                                                        int pitch, int units8, uint32_t* __restrict__ out8,
-                                                       float4* __restrict__ aux, int mode) {
+                                                       float4* __restrict__ aux, int mode,
+                                                       int* __restrict__ out_of_range) {
     const int lane = threadIdx.x & 63;
     const int64_t wave_global = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
@@ -51,6 +52,7 @@ __global__ __launch_bounds__(kBlock) void sq8_quantize(const float4* __restrict_
         }
         for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
         const float s = m / 127.0f;
+        if (out_of_range && lane == 0 && !sq8_in_range(m)) atomicOr(out_of_range, 1);
         long long sq = 0;
         double se = 0.0, sx = 0.0;
         for (int d = lane; d < dw; d += 64) {
@@ -86,12 +88,12 @@ __global__ __launch_bounds__(kBlock) void sq8_quantize(const float4* __restrict_
 }
 
 hipError_t launch_sq8_quantize(const float4* x, int64_t n, int units, int pitch, int units8, void* out8,
-                               float4* aux, int mode, hipStream_t s) {
+                               float4* aux, int mode, hipStream_t s, int* out_of_range) {
     if (n <= 0) return hipSuccess;
     int64_t blocks = (n + 3) / 4;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(sq8_quantize, dim3((unsigned)blocks), dim3(kBlock), 0, s, x, n, units, pitch, units8,
-                       static_cast<uint32_t*>(out8), aux, mode);
+                       static_cast<uint32_t*>(out8), aux, mode, out_of_range);
     return hipGetLastError();
 }
 
@@ -103,7 +105,7 @@ hipError_t launch_sq8_quantize(const float4* x, int64_t n, int units, int pitch,
 //   * the int8 quantisation (s = max|b|/127) and its bound terms qc[r];
 //     (an int16 query — 256× smaller query error — was measured: 4.4× fewer re-scored rows but a
 //     slower scan, its extra sdot4 work is not free at the HBM ceiling; so int8 it is)
-//   * flags[r] = 0.
+//   * flags[r] = 0, or kQueryOutOfRange for a query outside the certificate's range (osk_device.h).
 // ------------------------------------------------------------------------------------------------
 //   Q6 (single queries of the 6-bit tier, osk_sq6.hip): also its second quantisation of the query, to
 //   [-119, 119] (s6 = max|b|/119), split into signed nibbles b = 16·bh + bl and written in sq6_scan's
@@ -231,7 +233,7 @@ __global__ __launch_bounds__(kBlock) void sq8_prep(const float* __restrict__ src
         };
         qc[r] = terms(0, s8);
         if constexpr (Q6) q6.qc6[r] = terms(1, s6);
-        if (real) flags[r] = 0;
+        if (real) flags[r] = sq8_in_range(m) ? 0 : kQueryOutOfRange;
     }
 }
 
@@ -1335,7 +1337,8 @@ __global__ __launch_bounds__(kSettleThreads) void sq8_settle(SettleParams p) {
     const SegDev seg0 = p.segs[0];   // the common case (one segment per view) needs no lookup below
     if (tid == 0) {
         s_nc = 0;
-        s_exact = p.force_fail ? (nt >= 32 ? 0xFFFFFFFFu : (1u << nt) - 1u) : 0u;
+        // (a query outside the certificate's range: its lists mean nothing, every list is re-scanned exactly)
+        s_exact = (p.force_fail || (p.flags[q] & kQueryOutOfRange)) ? (nt >= 32 ? 0xFFFFFFFFu : (1u << nt) - 1u) : 0u;
     }
     if (tid < 64) s_top[tid] = 0ull;
 
@@ -1399,7 +1402,7 @@ __global__ __launch_bounds__(kSettleThreads) void sq8_settle(SettleParams p) {
     if (p.trace && tid == 0) p.trace[((size_t)q * p.n_slices + g) * 8 + 2] = wall_clock64();
     if (tid == 0) {
         if (exact) {
-            if (atomicOr(&p.flags[q], 1) == 0) atomicAdd(&p.counters[0], 1ull);
+            if ((atomicOr(&p.flags[q], 1) & 1) == 0) atomicAdd(&p.counters[0], 1ull);
             atomicAdd(&p.counters[2], (unsigned long long)__popc(exact));
         }
         if (nc) atomicAdd(&p.counters[1], (unsigned long long)nc);
@@ -1615,6 +1618,8 @@ __global__ __launch_bounds__(kWideSettleThreads) void sq8_settle_wide(SettlePara
     const int k = p.k, sim = p.sim;
     const int l0 = 4 * p.shard_tile_begin[sh], l1 = 4 * p.shard_tile_begin[sh + 1];
     const uint32_t* __restrict__ lm = p.list_lbmax + (size_t)q * p.n_lists;
+    // a query outside the certificate's range (sq8_prep): every list of the shard is re-scanned exactly
+    const bool qopen = (p.flags[q] & kQueryOutOfRange) != 0;
     // (a) bucket maxima: thread t takes lists l0 + t + 1024j (bucket t mod 64, 16 threads per bucket)
     uint32_t mx = 0u;
     for (int l = l0 + tid; l < l1; l += kWideSettleThreads) mx = max(mx, lm[l]);
@@ -1684,9 +1689,10 @@ __global__ __launch_bounds__(kWideSettleThreads) void sq8_settle_wide(SettlePara
                 const int l = c0 + 4 * (i0 + u * kWideSettleWaves) + (lane >> 4);
                 const uint64_t key = (in[u] && lmv[u] != 0u) ? kv[u] : 0ull;
                 const bool reach = key && (uint32_t)(key >> 32) >= Lb;
-                const uint64_t full = __ballot(reach && e == kKQ - 1);   // the list's 16th key reaches L
+                const bool redo = (qopen ? in[u] : reach) && e == kKQ - 1;
+                const uint64_t full = __ballot(redo);   // the list's 16th key reaches L
                 const bool exact = (full >> (lane | 15)) & 1ull;
-                if (reach && e == kKQ - 1) s_exact[atomicAdd(&s_ne, 1)] = l;
+                if (redo) s_exact[atomicAdd(&s_ne, 1)] = l;
                 if (reach && !exact) s_cand[atomicAdd(&s_nc, 1)] = 0xFFFFFFFFu - (uint32_t)key;
             }
         }
@@ -1728,7 +1734,7 @@ __global__ __launch_bounds__(kWideSettleThreads) void sq8_settle_wide(SettlePara
     }
     if (tid == 0) {
         if (n_exact) {
-            if (atomicOr(&p.flags[q], 1) == 0) atomicAdd(&p.counters[0], 1ull);
+            if ((atomicOr(&p.flags[q], 1) & 1) == 0) atomicAdd(&p.counters[0], 1ull);
             atomicAdd(&p.counters[2], n_exact);
         }
         if (n_res) atomicAdd(&p.counters[1], n_res);
