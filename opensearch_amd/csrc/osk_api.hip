@@ -438,7 +438,7 @@ int32_t osk_seg_stage(int32_t device, const void* rows, int64_t n_rows, int32_t 
     int32_t rc = seg_alloc(device, n_rows, dim, encoding, similarity, max_doc, ord_to_doc, s);
     if (rc) return rc;
     hipStream_t st = device_stream(device);
-    const int64_t elem = encoding == ENC_FLOAT32 ? 4 : 1;
+    const int64_t elem = elem_bytes(encoding);
     const int64_t src_pitch = (int64_t)dim * elem;
     const int64_t dst_pitch = (int64_t)s->units * 16;
     if (n_rows > 0) {
@@ -464,7 +464,7 @@ int32_t osk_seg_stage_file(int32_t device, const char* path, int64_t data_offset
     int32_t rc = seg_alloc(device, n_rows, dim, encoding, similarity, max_doc, ord_to_doc, s);
     if (rc) return rc;
     hipStream_t st = device_stream(device);
-    const int64_t row_bytes = (int64_t)dim * (encoding == ENC_FLOAT32 ? 4 : 1);
+    const int64_t row_bytes = (int64_t)dim * elem_bytes(encoding);
     const int64_t bytes = n_rows * row_bytes;
     const int64_t dst_pitch = (int64_t)s->units * 16;
     if (n_rows > 0) {
@@ -544,7 +544,7 @@ int32_t osk_seg_stage_device(int32_t device, const void* d_rows, int64_t src_pit
     int32_t rc = seg_alloc(device, n_rows, dim, encoding, similarity, max_doc, ord_to_doc, s);
     if (rc) return rc;
     hipStream_t st = device_stream(device);
-    const int64_t elem = encoding == ENC_FLOAT32 ? 4 : 1;
+    const int64_t elem = elem_bytes(encoding);
     OSK_REQUIRE(src_pitch_bytes >= (int64_t)dim * elem, "src_pitch_bytes < dim * element size");
     if (n_rows > 0)
         OSK_HIP(launch_pad_rows(d_rows, src_pitch_bytes, s->d_rows, (int64_t)s->units * 16, n_rows,
@@ -889,6 +889,13 @@ int32_t profile_begin(osk_view* v, hipStream_t st, bool record) {
     return OSK_OK;
 }
 
+// osk_view_profile(N): every N-th call stamps its scan launches (N = 1: every call); the event stamps cost
+// a few µs of stream time around the stamped launch, so a long timed loop samples instead of stamping all
+int32_t profile_sample(osk_view* v, hipStream_t st, bool record) {
+    v->profile = v->profile_every > 0 && v->profile_tick++ % (uint64_t)v->profile_every == 0;
+    return v->profile ? profile_begin(v, st, record) : OSK_OK;
+}
+
 int32_t profile_end(osk_view* v, hipStream_t st, bool record) {
     if (!v->profile) return OSK_OK;
     if (record) OSK_HIP(hipEventRecord(v->ev1, st));
@@ -900,6 +907,15 @@ int32_t profile_end(osk_view* v, hipStream_t st, bool record) {
 inline hipEvent_t launch_ev_start(const osk_view* v, int q0) { return v->profile && q0 == 0 ? v->ev0 : nullptr; }
 inline hipEvent_t launch_ev_stop(const osk_view* v, int q0, int nq) {
     return v->profile && q0 + kMaxNQ >= nq ? v->ev1 : nullptr;
+}
+
+// Nothing staged: every shard returns zero hits.
+int32_t zero_shard_hits(const osk_view* v, int nq, int k, uint64_t* d_shard_keys, int32_t* d_shard_counts,
+                        int64_t* d_visited, hipStream_t st) {
+    OSK_HIP(hipMemsetAsync(d_shard_keys, 0, sizeof(uint64_t) * nq * v->n_shards * k, st));
+    OSK_HIP(hipMemsetAsync(d_shard_counts, 0, sizeof(int32_t) * nq * v->n_shards, st));
+    if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
+    return OSK_OK;
 }
 
 // Streaming exact scan of queries already in the padded unit layout (≤ 8 per launch) + per-shard merge.
@@ -2140,6 +2156,47 @@ int32_t order_after_last(osk_view* v, hipStream_t st) {
     return OSK_OK;
 }
 
+int32_t upload_accept(osk_view* v, const uint64_t* const* accept, hipStream_t st, const uint64_t* const** d_accept) {
+    *d_accept = nullptr;
+    const int ns = (int)v->segs.size();
+    size_t words = 0;
+    bool any_bits = false;
+    for (int i = 0; accept && i < ns; ++i)
+        if (accept[i]) {
+            any_bits = true;
+            words += (size_t)(v->segs[i]->max_doc + 63) / 64;
+        }
+    if (!any_bits) return OSK_OK;
+    OSK_HIP(v->ws_accept.reserve(std::max<size_t>(8, words * 8)));
+    OSK_HIP(v->ws_accept_ptrs.reserve(sizeof(void*) * ns));
+    // the pointer table is staged in the view's pinned buffer: it is the source of an async copy and
+    // must outlive it (the stream is synchronised only at the end of the call)
+    OSK_HIP(v->h_accept_tab.reserve(sizeof(void*) * ns));
+    const uint64_t** ptrs = static_cast<const uint64_t**>(v->h_accept_tab.p);
+    size_t off = 0;
+    for (int i = 0; i < ns; ++i) {
+        ptrs[i] = nullptr;
+        if (!accept[i]) continue;
+        const size_t w = (size_t)(v->segs[i]->max_doc + 63) / 64;
+        ptrs[i] = v->ws_accept.as<uint64_t>() + off;
+        if (w) OSK_HIP(hipMemcpyAsync(const_cast<uint64_t*>(ptrs[i]), accept[i], w * 8, hipMemcpyHostToDevice, st));
+        off += w;
+    }
+    OSK_HIP(hipMemcpyAsync(v->ws_accept_ptrs.p, ptrs, sizeof(void*) * ns, hipMemcpyHostToDevice, st));
+    *d_accept = v->ws_accept_ptrs.as<const uint64_t*>();
+    return OSK_OK;
+}
+
+void MergedOut::copy_out(const char* stage, float* scores, int32_t* docs, int32_t* shard, int32_t* count,
+                         int64_t* total, float* max) const {
+    std::memcpy(scores, stage + o_sc, b_hits);
+    std::memcpy(docs, stage + o_doc, b_hits);
+    std::memcpy(shard, stage + o_sh, b_hits);
+    std::memcpy(count, stage + o_cnt, b_cnt);
+    std::memcpy(total, stage + o_tot, b_tot);
+    std::memcpy(max, stage + o_max, b_max);
+}
+
 // Core of osk_view_search_device (caller holds the view mutex; device already set).
 int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
                            const uint64_t* const* d_accept, uint64_t* d_shard_keys,
@@ -2149,18 +2206,10 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
     OSK_REQUIRE(d_queries && d_shard_keys && d_shard_counts, "null device buffer");
     int32_t rc0 = order_after_last(v, st);
     if (rc0) return rc0;
-    static const int kLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12},
-                                  {32, 8}, {64, 8}, {64, 16}};
-    const int UP = kLV[v->cfg][0] * kLV[v->cfg][1];
+    const int UP = cfg_padded_units(v->cfg);
     const int nq_pad = (nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;
-    const int64_t elem = v->enc == ENC_FLOAT32 ? 4 : 1;
 
-    if (v->n_tiles == 0) {   // nothing staged: every shard returns zero hits
-        OSK_HIP(hipMemsetAsync(d_shard_keys, 0, sizeof(uint64_t) * nq * v->n_shards * k, st));
-        OSK_HIP(hipMemsetAsync(d_shard_counts, 0, sizeof(int32_t) * nq * v->n_shards, st));
-        if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
-        return OSK_OK;
-    }
+    if (v->n_tiles == 0) return zero_shard_hits(v, nq, k, d_shard_keys, d_shard_counts, d_visited, st);
     OSK_HIP(v->ws_q.reserve((size_t)nq_pad * UP * 16));
     OSK_HIP(v->ws_qnorm.reserve(sizeof(float) * nq_pad));
     // Path cost model, measured end to end on MI355X, in µs for this view's rows R:
@@ -2203,15 +2252,12 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
     // queries → padded unit layout (zeros past dim and for the dummy queries of the last launch); the
     // prefilter path does this inside its own fused prep launch (so does the select path's bounds mode)
     if (!prefilter && !(select && sq8_on))
-        OSK_HIP(launch_prep_queries(d_queries, (int64_t)v->dim * elem, nq, v->ws_q.p, UP, nq_pad, st));
+        OSK_HIP(launch_prep_queries(d_queries, v->dim * elem_bytes(v->enc), nq, v->ws_q.p, UP, nq_pad, st));
 
     if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
 
-    int32_t rc;
-    // osk_view_profile(N): every N-th call stamps its scan launches (N = 1: every call); the event stamps cost
-    // a few µs of stream time around the stamped launch, so a long timed loop samples instead of stamping all
-    v->profile = v->profile_every > 0 && v->profile_tick++ % (uint64_t)v->profile_every == 0;
-    if (v->profile && (rc = profile_begin(v, st, batched)) != OSK_OK) return rc;
+    int32_t rc = profile_sample(v, st, batched);
+    if (rc) return rc;
     if (select) {
         rc = select_search(v, d_queries, nq, k, UP, d_accept, d_shard_keys, d_shard_counts, d_visited, st, sq8_on);
         if (rc == OSK_OK) rc = profile_end(v, st, false);
@@ -2239,21 +2285,17 @@ int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const 
     OSK_REQUIRE(d_queries && d_min_scores && d_docs && d_scores && d_count && d_total, "null device buffer");
     int32_t rc = order_after_last(v, st);
     if (rc) return rc;
-    static const int kLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12},
-                                  {32, 8}, {64, 8}, {64, 16}};
-    const int UP = kLV[v->cfg][0] * kLV[v->cfg][1];
+    const int UP = cfg_padded_units(v->cfg);
     const int nq_pad = (nq + kThrNQ - 1) / kThrNQ * kThrNQ;
-    const int64_t elem = v->enc == ENC_FLOAT32 ? 4 : 1;
     const int wpw = thr_words_per_wave(v->cfg, v->max_tile_rows);
     const size_t waves = (size_t)std::max(1, v->n_tiles) * 4;   // per query of a pass
     OSK_HIP(v->ws_q.reserve((size_t)nq_pad * UP * 16));
     OSK_HIP(v->ws_thr_mask.reserve(sizeof(uint64_t) * kThrNQ * waves * wpw));
     OSK_HIP(v->ws_thr_wcounts.reserve(sizeof(int32_t) * kThrNQ * waves));
     OSK_HIP(v->ws_thr_offsets.reserve(sizeof(int64_t) * kThrNQ * waves));
-    OSK_HIP(launch_prep_queries(d_queries, (int64_t)v->dim * elem, nq, v->ws_q.p, UP, nq_pad, st));
+    OSK_HIP(launch_prep_queries(d_queries, v->dim * elem_bytes(v->enc), nq, v->ws_q.p, UP, nq_pad, st));
     if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
-    v->profile = v->profile_every > 0 && v->profile_tick++ % (uint64_t)v->profile_every == 0;
-    if (v->profile && (rc = profile_begin(v, st, false)) != OSK_OK) return rc;
+    if ((rc = profile_sample(v, st, false)) != OSK_OK) return rc;
 
     ThrParams p{};
     p.segs = v->d_segs.as<SegDev>();
@@ -2308,26 +2350,19 @@ int32_t view_nested_device(osk_view* v, const void* d_queries, int nq, int k, co
     int32_t rc = order_after_last(v, st);
     if (rc) return rc;
     if ((rc = ensure_nested(v, st)) != OSK_OK) return rc;
-    if (v->n_tiles == 0) {   // nothing staged: every shard returns zero hits
-        OSK_HIP(hipMemsetAsync(d_shard_keys, 0, sizeof(uint64_t) * nq * v->n_shards * k, st));
-        OSK_HIP(hipMemsetAsync(d_shard_counts, 0, sizeof(int32_t) * nq * v->n_shards, st));
-        if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
+    if (v->n_tiles == 0) {
         v->nest_calls += 1;
-        return OSK_OK;
+        return zero_shard_hits(v, nq, k, d_shard_keys, d_shard_counts, d_visited, st);
     }
-    static const int kLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12},
-                                  {32, 8}, {64, 8}, {64, 16}};
-    const int UP = kLV[v->cfg][0] * kLV[v->cfg][1];
+    const int UP = cfg_padded_units(v->cfg);
     const int nq_pad = (nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;
-    const int64_t elem = v->enc == ENC_FLOAT32 ? 4 : 1;
     const size_t P = (size_t)v->nest_parents;
     OSK_HIP(v->ws_q.reserve((size_t)nq_pad * UP * 16));
     OSK_HIP(v->ws_nest_best.reserve(sizeof(uint64_t) * (size_t)std::min(nq, kMaxNQ) * P));
     OSK_HIP(v->ws_nest_cand.reserve(sizeof(uint64_t) * (size_t)nq * v->n_ptiles * k));
-    OSK_HIP(launch_prep_queries(d_queries, (int64_t)v->dim * elem, nq, v->ws_q.p, UP, nq_pad, st));
+    OSK_HIP(launch_prep_queries(d_queries, v->dim * elem_bytes(v->enc), nq, v->ws_q.p, UP, nq_pad, st));
     if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
-    v->profile = v->profile_every > 0 && v->profile_tick++ % (uint64_t)v->profile_every == 0;
-    if (v->profile && (rc = profile_begin(v, st, false)) != OSK_OK) return rc;
+    if ((rc = profile_sample(v, st, false)) != OSK_OK) return rc;
 
     NestParams p{};
     p.segs = v->d_segs.as<SegDev>();
@@ -2362,6 +2397,56 @@ int32_t view_nested_device(osk_view* v, const void* d_queries, int nq, int k, co
 
 }  // namespace osk
 
+namespace {
+
+// The single-segment view behind the segment entries, created on first use.  seg->mu guards only the
+// creation: it is never held across a search.
+int32_t seg_self_view(osk_seg* seg, osk_view** out) {
+    std::lock_guard<std::mutex> lk(seg->mu);
+    if (!seg->self_view) {
+        osk_seg* one[1] = {seg};
+        int32_t rc = osk_view_create(one, 1, nullptr, nullptr, 1, nullptr, &seg->self_view);
+        if (rc) return rc;
+        // owned by the segment: it must not keep the segment alive
+        seg->self_view->holds_refs = false;
+        seg->refs.fetch_sub(1);
+    }
+    *out = seg->self_view;
+    return OSK_OK;
+}
+
+// One synchronous host call on a view: a leased workspace slot (the view or a replica) and its stream, the
+// slot's mutex, the workspace ordered after the slot's previous call, the call timer.  Members are
+// destroyed in reverse order: the slot's mutex is released before the lease.
+struct HostCall {
+    ViewLease lease;
+    std::unique_lock<std::mutex> lock;
+    CallTimer timer;
+    osk_view* v = nullptr;
+    hipStream_t st = nullptr;
+    int32_t begin(osk_view* root) {
+        int32_t rc = lease_view(root, lease);
+        if (rc) return rc;
+        v = lease.v;
+        st = lease.st;
+        lock = std::unique_lock<std::mutex>(v->mu);
+        if ((rc = order_after_last(v, st)) != OSK_OK) return rc;
+        return timer.begin(v, st);
+    }
+    int32_t finish() {   // after the call's last enqueue: the results are in the pinned stage on return
+        int32_t rc = timer.end();
+        if (rc) return rc;
+        OSK_HIP(hipStreamSynchronize(st));
+        return timer.publish();
+    }
+};
+
+// The device core behind a host k-NN entry: view_search_device or view_nested_device.
+using ShardTopK = int32_t (*)(osk_view*, const void*, int, int, const uint64_t* const*, uint64_t*, int32_t*, int64_t*,
+                              hipStream_t);
+
+}  // namespace
+
 extern "C" {
 
 int32_t osk_view_search_device(osk_view* view, const void* d_queries, int32_t n_queries, int32_t k,
@@ -2372,7 +2457,7 @@ int32_t osk_view_search_device(osk_view* view, const void* d_queries, int32_t n_
     OSK_REQUIRE(view != nullptr, "view is null");
     int32_t rc = check_device(view->device);
     if (rc) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(view->device);
+    hipStream_t st = stream_or_default(stream, view->device);
     std::lock_guard<std::mutex> lk(view->mu);
     return view_search_device(view, d_queries, n_queries, k, d_accept, d_shard_keys, d_shard_counts,
                               d_visited, st);
@@ -2393,7 +2478,7 @@ int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, 
     if (rc) return rc;
     rc = check_device(view->device);
     if (rc) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(view->device);
+    hipStream_t st = stream_or_default(stream, view->device);
     std::lock_guard<std::mutex> lk(view->mu);
     return view_threshold_device(view, d_queries, n_queries, d_min_scores, d_accept, cap, d_docs, d_scores, d_count,
                                  d_total, d_visited, st);
@@ -2425,7 +2510,7 @@ int32_t osk_view_search_nested_device(osk_view* view, const void* d_queries, int
     if (rc) return rc;
     rc = check_device(view->device);
     if (rc) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(view->device);
+    hipStream_t st = stream_or_default(stream, view->device);
     std::lock_guard<std::mutex> lk(view->mu);
     return view_nested_device(view, d_queries, n_queries, k, d_accept, d_shard_keys, d_shard_counts, d_visited, st);
     OSK_GUARD_END
@@ -2513,7 +2598,7 @@ int32_t osk_merge_device(int32_t device, const uint64_t* d_shard_keys, const int
                 "null device buffer");
     int32_t rc = check_device(device);
     if (rc) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(device);
+    hipStream_t st = stream_or_default(stream, device);
     OSK_HIP(launch_coord_reduce(d_shard_keys, d_shard_counts, d_shard_index, n_queries, 1, n_shards, k,
                                from, size, d_scores, d_docs, d_shard_out, d_count, d_total_hits,
                                d_max_score, st));
@@ -2537,7 +2622,7 @@ int32_t osk_merge_device_ranked(int32_t device, const uint64_t* d_keys, int32_t 
                 "null device buffer");
     int32_t rc = check_device(device);
     if (rc) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(device);
+    hipStream_t st = stream_or_default(stream, device);
     OSK_HIP(launch_coord_reduce(d_keys, nullptr, d_shard_index, n_queries, n_ranks, shards_per_rank, k, from,
                                size, d_scores, d_docs, d_shard_out, d_count, d_total_hits, d_max_score, st));
     return OSK_OK;
@@ -2722,7 +2807,7 @@ int32_t osk_view_scan_time(osk_view* v, double* total_ms, int64_t* calls) {
 static int32_t view_search_host(osk_view* v, const void* queries, int32_t n_queries, int32_t k, int32_t from,
                                 int32_t size, const uint64_t* const* accept, float* out_scores,
                                 int32_t* out_docs, int32_t* out_shard_index, int32_t* out_count,
-                                int64_t* out_total_hits, float* out_max_score, bool nested = false) {
+                                int64_t* out_total_hits, float* out_max_score, ShardTopK core) {
     OSK_GUARD_BEGIN
     clear_error();
     OSK_REQUIRE(v != nullptr && queries != nullptr, "null argument");
@@ -2732,90 +2817,38 @@ static int32_t view_search_host(osk_view* v, const void* queries, int32_t n_quer
     OSK_REQUIRE(from >= 0 && size >= 1, "bad from/size");
     int32_t rc = check_device(v->device);
     if (rc) return rc;
-    ViewLease lease;   // a workspace slot (this view or a replica) and its stream, for this call
-    rc = lease_view(v, lease);
-    if (rc) return rc;
-    v = lease.v;
-    hipStream_t st = lease.st;
-    std::lock_guard<std::mutex> lk(v->mu);
-    rc = order_after_last(v, st);
-    if (rc) return rc;
-    const int nq = n_queries, S = v->n_shards, ns = (int)v->segs.size();
-    const int64_t elem = v->enc == ENC_FLOAT32 ? 4 : 1;
-    const size_t qbytes = (size_t)nq * v->dim * elem;
-    CallTimer timer;
-    if ((rc = timer.begin(v, st)) != OSK_OK) return rc;
-
-    // accept bitsets → device
+    HostCall call;
+    if ((rc = call.begin(v)) != OSK_OK) return rc;
+    v = call.v;
+    hipStream_t st = call.st;
+    const int nq = n_queries, S = v->n_shards;
+    const size_t qbytes = (size_t)nq * v->dim * elem_bytes(v->enc);
     const uint64_t* const* d_acc = nullptr;
-    bool any_bits = false;   // no leaf with a bitset = no filter (the unfiltered scan instances)
-    for (int i = 0; accept && i < ns; ++i) any_bits |= accept[i] != nullptr;
-    if (any_bits) {
-        size_t words = 0;
-        for (int i = 0; i < ns; ++i)
-            if (accept[i]) words += (size_t)(v->segs[i]->max_doc + 63) / 64;
-        OSK_HIP(v->ws_accept.reserve(std::max<size_t>(8, words * 8)));
-        OSK_HIP(v->ws_accept_ptrs.reserve(sizeof(void*) * ns));
-        // the pointer table is staged in the view's pinned buffer: it is the source of an async copy and
-        // must outlive it (the stream is synchronised only at the end of the call)
-        OSK_HIP(v->h_accept_tab.reserve(sizeof(void*) * ns));
-        const uint64_t** ptrs = static_cast<const uint64_t**>(v->h_accept_tab.p);
-        size_t off = 0;
-        for (int i = 0; i < ns; ++i) {
-            ptrs[i] = nullptr;
-            if (!accept[i]) continue;
-            const size_t w = (size_t)(v->segs[i]->max_doc + 63) / 64;
-            ptrs[i] = v->ws_accept.as<uint64_t>() + off;
-            OSK_HIP(hipMemcpyAsync(const_cast<uint64_t*>(ptrs[i]), accept[i], w * 8,
-                                   hipMemcpyHostToDevice, st));
-            off += w;
-        }
-        OSK_HIP(hipMemcpyAsync(v->ws_accept_ptrs.p, ptrs, sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-        d_acc = v->ws_accept_ptrs.as<const uint64_t*>();
-    }
+    if ((rc = upload_accept(v, accept, st, &d_acc)) != OSK_OK) return rc;
     OSK_HIP(v->ws_qin.reserve(std::max<size_t>(16, qbytes)));
     OSK_HIP(hipMemcpyAsync(v->ws_qin.p, queries, qbytes, hipMemcpyHostToDevice, st));
     OSK_HIP(v->ws_keys.reserve(sizeof(uint64_t) * (size_t)nq * S * k));
     OSK_HIP(v->ws_counts.reserve(sizeof(int32_t) * (size_t)nq * S));
-    rc = nested ? view_nested_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
-                                     v->ws_counts.as<int32_t>(), nullptr, st)
-                : view_search_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
-                                     v->ws_counts.as<int32_t>(), nullptr, st);
+    rc = core(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(), v->ws_counts.as<int32_t>(), nullptr, st);
     if (rc) return rc;
-    // outputs: scores f32 | docs i32 | shard i32 | count i32 | total i64 | max f32
-    const size_t n_out = (size_t)nq * size;
-    const size_t b_sc = n_out * 4, b_doc = n_out * 4, b_sh = n_out * 4, b_cnt = nq * 4,
-                 b_tot = nq * 8, b_max = nq * 4;
-    const size_t o_sc = 0, o_doc = o_sc + b_sc, o_sh = o_doc + b_doc, o_cnt = o_sh + b_sh,
-                 o_tot = (o_cnt + b_cnt + 7) / 8 * 8, o_max = o_tot + b_tot,
-                 total_b = o_max + b_max;
-    OSK_HIP(v->ws_out.reserve(total_b));
-    char* ob = v->ws_out.as<char>();
+    const MergedOut out(nq, size);
+    OSK_HIP(v->ws_out.reserve(out.total_bytes));
+    const MergedOut::Ptrs o = out.at(v->ws_out.as<char>());
     OSK_HIP(launch_coord_reduce(v->ws_keys.as<uint64_t>(), v->ws_counts.as<int32_t>(),
-                               v->d_shard_index.as<int32_t>(), nq, 1, S, k, from, size,
-                               reinterpret_cast<float*>(ob + o_sc), reinterpret_cast<int32_t*>(ob + o_doc),
-                               reinterpret_cast<int32_t*>(ob + o_sh), reinterpret_cast<int32_t*>(ob + o_cnt),
-                               reinterpret_cast<int64_t*>(ob + o_tot), reinterpret_cast<float*>(ob + o_max),
-                               st));
-    OSK_HIP(v->h_stage.reserve(total_b));
-    OSK_HIP(hipMemcpyAsync(v->h_stage.p, ob, total_b, hipMemcpyDeviceToHost, st));
-    if ((rc = timer.end()) != OSK_OK) return rc;
-    OSK_HIP(hipStreamSynchronize(st));
-    if ((rc = timer.publish()) != OSK_OK) return rc;
-    const char* hb = static_cast<const char*>(v->h_stage.p);
-    std::memcpy(out_scores, hb + o_sc, b_sc);
-    std::memcpy(out_docs, hb + o_doc, b_doc);
-    std::memcpy(out_shard_index, hb + o_sh, b_sh);
-    std::memcpy(out_count, hb + o_cnt, b_cnt);
-    std::memcpy(out_total_hits, hb + o_tot, b_tot);
-    std::memcpy(out_max_score, hb + o_max, b_max);
+                               v->d_shard_index.as<int32_t>(), nq, 1, S, k, from, size, o.scores, o.docs, o.shard,
+                               o.count, o.total, o.max, st));
+    OSK_HIP(v->h_stage.reserve(out.total_bytes));
+    OSK_HIP(hipMemcpyAsync(v->h_stage.p, v->ws_out.p, out.total_bytes, hipMemcpyDeviceToHost, st));
+    if ((rc = call.finish()) != OSK_OK) return rc;
+    out.copy_out(static_cast<const char*>(v->h_stage.p), out_scores, out_docs, out_shard_index, out_count,
+                 out_total_hits, out_max_score);
     return OSK_OK;
     OSK_GUARD_END
 }
 
 static int32_t seg_search_host(osk_seg* seg, const void* queries, int32_t n_queries, int32_t k,
                                const uint64_t* accept_bits, float* out_scores, int32_t* out_docs,
-                               int32_t* out_count, int64_t* out_visited, bool nested = false) {
+                               int32_t* out_count, int64_t* out_visited, ShardTopK core) {
     OSK_GUARD_BEGIN
     clear_error();
     OSK_REQUIRE(seg != nullptr && queries != nullptr, "null argument");
@@ -2825,52 +2858,24 @@ static int32_t seg_search_host(osk_seg* seg, const void* queries, int32_t n_quer
     int32_t rc = check_device(seg->device);
     if (rc) return rc;
     osk_view* v;
-    {
-        std::lock_guard<std::mutex> lk(seg->mu);
-        if (!seg->self_view) {
-            osk_seg* one[1] = {seg};
-            rc = osk_view_create(one, 1, nullptr, nullptr, 1, nullptr, &seg->self_view);
-            if (rc) return rc;
-            // owned by the segment: it must not keep the segment alive
-            seg->self_view->holds_refs = false;
-            seg->refs.fetch_sub(1);
-        }
-        v = seg->self_view;
-    }
+    if ((rc = seg_self_view(seg, &v)) != OSK_OK) return rc;
     (void)hipSetDevice(seg->device);
-    ViewLease lease;   // a workspace slot (the self view or a replica) and its stream, for this call
-    rc = lease_view(v, lease);
-    if (rc) return rc;
-    v = lease.v;
-    hipStream_t st = lease.st;
-    std::lock_guard<std::mutex> lk(v->mu);
-    rc = order_after_last(v, st);
-    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin(v)) != OSK_OK) return rc;
+    v = call.v;
+    hipStream_t st = call.st;
     const int nq = n_queries;
-    const int64_t elem = seg->enc == ENC_FLOAT32 ? 4 : 1;
-    const size_t qbytes = (size_t)nq * seg->dim * elem;
-    CallTimer timer;
-    if ((rc = timer.begin(v, st)) != OSK_OK) return rc;
+    const size_t qbytes = (size_t)nq * seg->dim * elem_bytes(seg->enc);
+    const uint64_t* const acc[1] = {accept_bits};
     const uint64_t* const* d_acc = nullptr;
-    if (accept_bits) {
-        const size_t w = (size_t)(seg->max_doc + 63) / 64;
-        OSK_HIP(v->ws_accept.reserve(std::max<size_t>(8, w * 8)));
-        OSK_HIP(v->ws_accept_ptrs.reserve(sizeof(void*)));
-        if (w) OSK_HIP(hipMemcpyAsync(v->ws_accept.p, accept_bits, w * 8, hipMemcpyHostToDevice, st));
-        // the source of the async copy must outlive it: a view member (the call synchronises below)
-        v->h_accept_ptr = v->ws_accept.as<uint64_t>();
-        OSK_HIP(hipMemcpyAsync(v->ws_accept_ptrs.p, &v->h_accept_ptr, sizeof(void*), hipMemcpyHostToDevice, st));
-        d_acc = v->ws_accept_ptrs.as<const uint64_t*>();
-    }
+    if ((rc = upload_accept(v, acc, st, &d_acc)) != OSK_OK) return rc;
     OSK_HIP(v->ws_qin.reserve(std::max<size_t>(16, qbytes)));
     OSK_HIP(hipMemcpyAsync(v->ws_qin.p, queries, qbytes, hipMemcpyHostToDevice, st));
     OSK_HIP(v->ws_keys.reserve(sizeof(uint64_t) * (size_t)nq * k));
     OSK_HIP(v->ws_counts.reserve(sizeof(int32_t) * (size_t)nq));
     OSK_HIP(v->ws_visited.reserve(sizeof(int64_t)));
-    rc = nested ? view_nested_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
-                                     v->ws_counts.as<int32_t>(), v->ws_visited.as<int64_t>(), st)
-                : view_search_device(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(),
-                                     v->ws_counts.as<int32_t>(), v->ws_visited.as<int64_t>(), st);
+    rc = core(v, v->ws_qin.p, nq, k, d_acc, v->ws_keys.as<uint64_t>(), v->ws_counts.as<int32_t>(),
+              v->ws_visited.as<int64_t>(), st);
     if (rc) return rc;
     const size_t kb = sizeof(uint64_t) * (size_t)nq * k, cb = sizeof(int32_t) * nq;
     OSK_HIP(v->h_stage.reserve(kb + cb + 8));
@@ -2878,9 +2883,7 @@ static int32_t seg_search_host(osk_seg* seg, const void* queries, int32_t n_quer
     OSK_HIP(hipMemcpyAsync(hb, v->ws_keys.p, kb, hipMemcpyDeviceToHost, st));
     OSK_HIP(hipMemcpyAsync(hb + kb, v->ws_counts.p, cb, hipMemcpyDeviceToHost, st));
     OSK_HIP(hipMemcpyAsync(hb + kb + cb, v->ws_visited.p, 8, hipMemcpyDeviceToHost, st));
-    if ((rc = timer.end()) != OSK_OK) return rc;
-    OSK_HIP(hipStreamSynchronize(st));
-    if ((rc = timer.publish()) != OSK_OK) return rc;
+    if ((rc = call.finish()) != OSK_OK) return rc;
     const uint64_t* keys = reinterpret_cast<const uint64_t*>(hb);
     const int32_t* cnt = reinterpret_cast<const int32_t*>(hb + kb);
     int64_t visited;
@@ -3007,15 +3010,15 @@ int32_t osk_view_search(osk_view* v, const void* queries, int32_t n_queries, int
     for (int i = 0; accept && i < (int)v->segs.size(); ++i) any_bits |= accept[i] != nullptr;
     if (any_bits || !g_tuning.host_batching || n_queries < 1 || n_queries > kBatchMaxQueries)
         return view_search_host(v, queries, n_queries, k, from, size, accept, out_scores, out_docs, out_shard_index,
-                                out_count, out_total_hits, out_max_score);
+                                out_count, out_total_hits, out_max_score, view_search_device);
     BatchReq me{queries, n_queries, k, from, size, out_scores, out_docs, out_shard_index, out_count,
                 out_total_hits, out_max_score, nullptr};
-    const size_t qrow = (size_t)v->dim * (v->enc == ENC_FLOAT32 ? 4 : 1);
+    const size_t qrow = (size_t)v->dim * elem_bytes(v->enc);
     return batched_call(v, me, [&](const std::vector<BatchReq*>& batch, int total) -> int32_t {
         if (batch.size() == 1) {
             BatchReq* r = batch[0];
             return view_search_host(v, r->queries, r->nq, r->k, r->from, r->size, nullptr, r->sc, r->docs, r->shard,
-                                    r->cnt, r->tot, r->mx);
+                                    r->cnt, r->tot, r->mx, view_search_device);
         }
         const int sz = batch[0]->size;
         std::vector<char> q((size_t)total * qrow);
@@ -3028,7 +3031,8 @@ int32_t osk_view_search(osk_view* v, const void* queries, int32_t n_queries, int
             off += r->nq;
         }
         const int32_t rc = view_search_host(v, q.data(), total, batch[0]->k, batch[0]->from, sz, nullptr, sc.data(),
-                                            dc.data(), sh.data(), cnt.data(), tot.data(), mx.data());
+                                            dc.data(), sh.data(), cnt.data(), tot.data(), mx.data(),
+                                            view_search_device);
         if (rc) return rc;
         off = 0;
         for (BatchReq* r : batch) {
@@ -3054,25 +3058,18 @@ int32_t osk_seg_search(osk_seg* seg, const void* queries, int32_t n_queries, int
     clear_error();
     OSK_REQUIRE(seg != nullptr && queries != nullptr, "null argument");
     if (accept_bits || !g_tuning.host_batching || n_queries < 1 || n_queries > kBatchMaxQueries)
-        return seg_search_host(seg, queries, n_queries, k, accept_bits, out_scores, out_docs, out_count, out_visited);
+        return seg_search_host(seg, queries, n_queries, k, accept_bits, out_scores, out_docs, out_count, out_visited,
+                               view_search_device);
     osk_view* root;
-    {
-        std::lock_guard<std::mutex> lk(seg->mu);
-        if (!seg->self_view) {
-            osk_seg* one[1] = {seg};
-            int32_t rc = osk_view_create(one, 1, nullptr, nullptr, 1, nullptr, &seg->self_view);
-            if (rc) return rc;
-            seg->self_view->holds_refs = false;   // owned by the segment: must not keep it alive
-            seg->refs.fetch_sub(1);
-        }
-        root = seg->self_view;
-    }
+    const int32_t rc_view = seg_self_view(seg, &root);
+    if (rc_view) return rc_view;
     BatchReq me{queries, n_queries, k, 0, k, out_scores, out_docs, nullptr, out_count, nullptr, nullptr, out_visited};
-    const size_t qrow = (size_t)seg->dim * (seg->enc == ENC_FLOAT32 ? 4 : 1);
+    const size_t qrow = (size_t)seg->dim * elem_bytes(seg->enc);
     return batched_call(root, me, [&](const std::vector<BatchReq*>& batch, int total) -> int32_t {
         if (batch.size() == 1) {
             BatchReq* r = batch[0];
-            return seg_search_host(seg, r->queries, r->nq, r->k, nullptr, r->sc, r->docs, r->cnt, r->visited);
+            return seg_search_host(seg, r->queries, r->nq, r->k, nullptr, r->sc, r->docs, r->cnt, r->visited,
+                                   view_search_device);
         }
         const int kk = batch[0]->k;
         std::vector<char> q((size_t)total * qrow);
@@ -3084,7 +3081,8 @@ int32_t osk_seg_search(osk_seg* seg, const void* queries, int32_t n_queries, int
             std::memcpy(q.data() + (size_t)off * qrow, r->queries, (size_t)r->nq * qrow);
             off += r->nq;
         }
-        const int32_t rc = seg_search_host(seg, q.data(), total, kk, nullptr, sc.data(), dc.data(), cnt.data(), vis.data());
+        const int32_t rc = seg_search_host(seg, q.data(), total, kk, nullptr, sc.data(), dc.data(), cnt.data(),
+                                           vis.data(), view_search_device);
         if (rc) return rc;
         off = 0;
         for (BatchReq* r : batch) {
@@ -3106,42 +3104,15 @@ int32_t osk_seg_search(osk_seg* seg, const void* queries, int32_t n_queries, int
 static int32_t threshold_host(osk_view* v, const void* queries, int32_t n_queries, const float* min_scores,
                               const uint64_t* const* accept, int32_t cap, int32_t* out_docs, float* out_scores,
                               int32_t* out_count, int64_t* out_total, int64_t* out_visited) {
-    ViewLease lease;
-    int32_t rc = lease_view(v, lease);
+    HostCall call;
+    int32_t rc = call.begin(v);
     if (rc) return rc;
-    v = lease.v;
-    hipStream_t st = lease.st;
-    std::lock_guard<std::mutex> lk(v->mu);
-    rc = order_after_last(v, st);
-    if (rc) return rc;
+    v = call.v;
+    hipStream_t st = call.st;
     const int nq = n_queries, S = v->n_shards, ns = (int)v->segs.size();
-    const int64_t elem = v->enc == ENC_FLOAT32 ? 4 : 1;
-    const size_t qbytes = (size_t)nq * v->dim * elem;
-    CallTimer timer;
-    if ((rc = timer.begin(v, st)) != OSK_OK) return rc;
+    const size_t qbytes = (size_t)nq * v->dim * elem_bytes(v->enc);
     const uint64_t* const* d_acc = nullptr;
-    bool any_bits = false;
-    for (int i = 0; accept && i < ns; ++i) any_bits |= accept[i] != nullptr;
-    if (any_bits) {
-        size_t words = 0;
-        for (int i = 0; i < ns; ++i)
-            if (accept[i]) words += (size_t)(v->segs[i]->max_doc + 63) / 64;
-        OSK_HIP(v->ws_accept.reserve(std::max<size_t>(8, words * 8)));
-        OSK_HIP(v->ws_accept_ptrs.reserve(sizeof(void*) * ns));
-        OSK_HIP(v->h_accept_tab.reserve(sizeof(void*) * ns));   // source of an async copy: outlives it
-        const uint64_t** ptrs = static_cast<const uint64_t**>(v->h_accept_tab.p);
-        size_t off = 0;
-        for (int i = 0; i < ns; ++i) {
-            ptrs[i] = nullptr;
-            if (!accept[i]) continue;
-            const size_t w = (size_t)(v->segs[i]->max_doc + 63) / 64;
-            ptrs[i] = v->ws_accept.as<uint64_t>() + off;
-            if (w) OSK_HIP(hipMemcpyAsync(const_cast<uint64_t*>(ptrs[i]), accept[i], w * 8, hipMemcpyHostToDevice, st));
-            off += w;
-        }
-        OSK_HIP(hipMemcpyAsync(v->ws_accept_ptrs.p, ptrs, sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-        d_acc = v->ws_accept_ptrs.as<const uint64_t*>();
-    }
+    if ((rc = upload_accept(v, accept, st, &d_acc)) != OSK_OK) return rc;
     OSK_HIP(v->ws_qin.reserve(std::max<size_t>(16, qbytes)));
     OSK_HIP(hipMemcpyAsync(v->ws_qin.p, queries, qbytes, hipMemcpyHostToDevice, st));
     OSK_HIP(v->ws_thr_min.reserve(sizeof(float) * nq));
@@ -3159,9 +3130,7 @@ static int32_t threshold_host(osk_view* v, const void* queries, int32_t n_querie
     if (rc) return rc;
     OSK_HIP(v->h_stage.reserve(total_b));
     OSK_HIP(hipMemcpyAsync(v->h_stage.p, ob, total_b, hipMemcpyDeviceToHost, st));
-    if ((rc = timer.end()) != OSK_OK) return rc;
-    OSK_HIP(hipStreamSynchronize(st));
-    if ((rc = timer.publish()) != OSK_OK) return rc;
+    if ((rc = call.finish()) != OSK_OK) return rc;
     const char* hb = static_cast<const char*>(v->h_stage.p);
     std::memcpy(out_docs, hb + o_doc, n_out * 4);
     std::memcpy(out_scores, hb + o_sc, n_out * 4);
@@ -3203,22 +3172,12 @@ int32_t osk_seg_search_threshold(osk_seg* seg, const void* queries, int32_t n_qu
     rc = check_device(seg->device);
     if (rc) return rc;
     osk_view* v;
-    {
-        std::lock_guard<std::mutex> lk(seg->mu);
-        if (!seg->self_view) {
-            osk_seg* one[1] = {seg};
-            rc = osk_view_create(one, 1, nullptr, nullptr, 1, nullptr, &seg->self_view);
-            if (rc) return rc;
-            seg->self_view->holds_refs = false;   // owned by the segment: it must not keep the segment alive
-            seg->refs.fetch_sub(1);
-        }
-        v = seg->self_view;
-    }
+    if ((rc = seg_self_view(seg, &v)) != OSK_OK) return rc;
     (void)hipSetDevice(seg->device);
-    const uint64_t* acc[1] = {accept_bits};
+    const uint64_t* const acc[1] = {accept_bits};
     int64_t visited = 0;
-    rc = threshold_host(v, queries, n_queries, min_scores, accept_bits ? acc : nullptr, cap, out_docs, out_scores,
-                        out_count, out_total, &visited);
+    rc = threshold_host(v, queries, n_queries, min_scores, acc, cap, out_docs, out_scores, out_count, out_total,
+                        &visited);
     if (rc) return rc;
     for (int q = 0; out_visited && q < n_queries; ++q) out_visited[q] = visited;
     return OSK_OK;
@@ -3243,7 +3202,7 @@ int32_t osk_view_search_nested(osk_view* view, const void* queries, int32_t n_qu
     rc = any_device();
     if (rc) return rc;
     return view_search_host(view, queries, n_queries, k, from, size, accept, out_scores, out_docs, out_shard_index,
-                            out_count, out_total_hits, out_max_score, true);
+                            out_count, out_total_hits, out_max_score, view_nested_device);
     OSK_GUARD_END
 }
 
@@ -3258,7 +3217,8 @@ int32_t osk_seg_search_nested(osk_seg* seg, const void* queries, int32_t n_queri
     if (rc) return rc;
     rc = any_device();
     if (rc) return rc;
-    return seg_search_host(seg, queries, n_queries, k, accept_bits, out_scores, out_docs, out_count, out_visited, true);
+    return seg_search_host(seg, queries, n_queries, k, accept_bits, out_scores, out_docs, out_count, out_visited,
+                           view_nested_device);
     OSK_GUARD_END
 }
 

@@ -368,7 +368,7 @@ int32_t fill_block(osk_view* v, const void* d_queries, int nq, int k, const uint
     // (cap: the device entry's fixed block — the call's lists at its start, the header at cap->keys)
     const Block B = cap ? *cap : block_of(nq, k, spr);
     OSK_HIP(v->ws_xkeys.reserve(sizeof(uint64_t) * std::max(B.words, (size_t)nq * spr * k)));
-    const int64_t qbytes = (int64_t)nq * v->dim * (v->enc == ENC_FLOAT32 ? 4 : 1);
+    const int64_t qbytes = (int64_t)nq * v->dim * elem_bytes(v->enc);
     OSK_HIP(launch_xhdr_fill(v->ws_xkeys.as<uint64_t>() + B.keys, hw, d_queries, qbytes,
                              v->d_shard_index.as<int32_t>(), v->n_shards, spr, st));
     return search_padded(v, d_queries, nq, k, d_accept, spr, st);
@@ -588,7 +588,7 @@ int32_t osk_comm_all_gather(osk_comm* comm, const void* d_send, void* d_recv, in
     OSK_REQUIRE(comm->devices.size() == 1, "osk_comm_all_gather needs a one-device-per-process communicator");
     int32_t rc = check_device(comm->devices[0]);
     if (rc) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(comm->devices[0]);
+    hipStream_t st = stream_or_default(stream, comm->devices[0]);
     std::lock_guard<std::mutex> lk(comm->mu);
     OSK_HIP(enter_xstream(comm, 0, st));
 #ifdef OSK_TESTING
@@ -728,7 +728,7 @@ int32_t osk_shards_search_merge_device(osk_comm* comm, osk_view* view, const voi
     }
     int32_t rc = check_device(view->device);
     if (rc) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : device_stream(view->device);
+    hipStream_t st = stream_or_default(stream, view->device);
     // No refusal on the poison flag here: the previous call's reduce writes it asynchronously, so a rank
     // whose reduce had finished would refuse while a rank whose reduce had not would enter the all-gather
     // and wait forever.  Every call issues its collective; a poisoned communicator's reduce reports
@@ -844,7 +844,7 @@ int32_t osk_shards_search_merge(osk_comm* comm, osk_view* const* views, int32_t 
     std::lock_guard<std::mutex> lc(comm->mu);
     std::vector<std::unique_lock<std::mutex>> locks;
     std::vector<hipStream_t> sts(n_views);
-    const int64_t elem = views[0]->enc == ENC_FLOAT32 ? 4 : 1;
+    const int64_t elem = elem_bytes(views[0]->enc);
     const size_t qbytes = (size_t)n_queries * views[0]->dim * elem;
     size_t seg_off = 0;
     for (int i = 0; i < n_views; ++i) {
@@ -858,32 +858,11 @@ int32_t osk_shards_search_merge(osk_comm* comm, osk_view* const* views, int32_t 
         // queries and accept bitsets → this device
         OSK_HIP(v->ws_qin.reserve(std::max<size_t>(16, qbytes)));
         OSK_HIP(hipMemcpyAsync(v->ws_qin.p, queries, qbytes, hipMemcpyHostToDevice, sts[i]));
-        const int ns = (int)v->segs.size();
+        // (view i's leaves are accept[seg_off …]; v->mu is held until the streams are synchronised below)
         const uint64_t* const* d_acc = nullptr;
-        bool any = false;
-        for (int j = 0; accept && j < ns; ++j) any |= accept[seg_off + j] != nullptr;
-        if (any) {
-            size_t words = 0;
-            for (int j = 0; j < ns; ++j)
-                if (accept[seg_off + j]) words += (size_t)(v->segs[j]->max_doc + 63) / 64;
-            OSK_HIP(v->ws_accept.reserve(std::max<size_t>(8, words * 8)));
-            OSK_HIP(v->ws_accept_ptrs.reserve(sizeof(void*) * ns));
-            std::vector<const uint64_t*> ptrs(ns, nullptr);
-            size_t off = 0;
-            for (int j = 0; j < ns; ++j) {
-                if (!accept[seg_off + j]) continue;
-                const size_t w = (size_t)(v->segs[j]->max_doc + 63) / 64;
-                ptrs[j] = v->ws_accept.as<uint64_t>() + off;
-                OSK_HIP(hipMemcpyAsync(const_cast<uint64_t*>(ptrs[j]), accept[seg_off + j], w * 8,
-                                       hipMemcpyHostToDevice, sts[i]));
-                off += w;
-            }
-            OSK_HIP(hipMemcpyAsync(v->ws_accept_ptrs.p, ptrs.data(), sizeof(void*) * ns, hipMemcpyHostToDevice,
-                                   sts[i]));
-            OSK_HIP(hipStreamSynchronize(sts[i]));   // ptrs is a local
-            d_acc = v->ws_accept_ptrs.as<const uint64_t*>();
-        }
-        seg_off += ns;
+        rc = upload_accept(v, accept ? accept + seg_off : nullptr, sts[i], &d_acc);
+        if (rc) return rc;
+        seg_off += v->segs.size();
         OSK_HIP(v->ws_keys.reserve(sizeof(uint64_t) * (size_t)n_queries * v->n_shards * k));
         OSK_HIP(v->ws_counts.reserve(sizeof(int32_t) * (size_t)n_queries * v->n_shards));
         rc = view_search_device(v, v->ws_qin.p, n_queries, k, d_acc, v->ws_keys.as<uint64_t>(),
@@ -931,34 +910,23 @@ int32_t osk_shards_search_merge(osk_comm* comm, osk_view* const* views, int32_t 
     // the coordinator reduce on local device 0 (every local device holds the same image)
     osk_view* v0 = views[0];
     OSK_HIP(hipSetDevice(v0->device));
-    const size_t n_out = (size_t)n_queries * size;
-    const size_t b_sc = n_out * 4, b_doc = n_out * 4, b_sh = n_out * 4, b_cnt = (size_t)n_queries * 4,
-                 b_tot = (size_t)n_queries * 8, b_max = (size_t)n_queries * 4;
-    const size_t o_sc = 0, o_doc = o_sc + b_sc, o_sh = o_doc + b_doc, o_cnt = o_sh + b_sh,
-                 o_tot = (o_cnt + b_cnt + 7) / 8 * 8, o_max = o_tot + b_tot, total_b = o_max + b_max;
-    OSK_HIP(v0->ws_xout.reserve(total_b));
-    char* ob = v0->ws_xout.as<char>();
+    const MergedOut out(n_queries, size);
+    OSK_HIP(v0->ws_xout.reserve(out.total_bytes));
+    const MergedOut::Ptrs o = out.at(v0->ws_xout.as<char>());
     const int32_t* sidx = nullptr;
     const XLayout x = image_layout(comm, image, B, &sidx);
-    OSK_HIP(launch_coord_reduce(image, nullptr, sidx, n_queries, comm->world, spr, k, from, size,
-                               reinterpret_cast<float*>(ob + o_sc), reinterpret_cast<int32_t*>(ob + o_doc),
-                               reinterpret_cast<int32_t*>(ob + o_sh), reinterpret_cast<int32_t*>(ob + o_cnt),
-                               reinterpret_cast<int64_t*>(ob + o_tot), reinterpret_cast<float*>(ob + o_max), sts[0], x));
-    OSK_HIP(v0->h_stage.reserve(total_b));
-    OSK_HIP(hipMemcpyAsync(v0->h_stage.p, ob, total_b, hipMemcpyDeviceToHost, sts[0]));
+    OSK_HIP(launch_coord_reduce(image, nullptr, sidx, n_queries, comm->world, spr, k, from, size, o.scores, o.docs,
+                               o.shard, o.count, o.total, o.max, sts[0], x));
+    OSK_HIP(v0->h_stage.reserve(out.total_bytes));
+    OSK_HIP(hipMemcpyAsync(v0->h_stage.p, v0->ws_xout.p, out.total_bytes, hipMemcpyDeviceToHost, sts[0]));
     for (int i = 0; i < n_views; ++i) {
         OSK_HIP(hipSetDevice(views[i]->device));
         OSK_HIP(hipStreamSynchronize(sts[i]));
     }
     rc = poisoned(comm);   // the ranks issued different calls: no result
     if (rc) return rc;
-    const char* hb = static_cast<const char*>(v0->h_stage.p);
-    std::memcpy(out_scores, hb + o_sc, b_sc);
-    std::memcpy(out_docs, hb + o_doc, b_doc);
-    std::memcpy(out_shard_index, hb + o_sh, b_sh);
-    std::memcpy(out_count, hb + o_cnt, b_cnt);
-    std::memcpy(out_total_hits, hb + o_tot, b_tot);
-    std::memcpy(out_max_score, hb + o_max, b_max);
+    out.copy_out(static_cast<const char*>(v0->h_stage.p), out_scores, out_docs, out_shard_index, out_count,
+                 out_total_hits, out_max_score);
     return OSK_OK;
     OSK_GUARD_END
 }

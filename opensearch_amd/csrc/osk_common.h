@@ -103,20 +103,9 @@ OSK_HD float score_i8(int sim, int32_t s, int32_t qn, int32_t xn, int dim) {
 // partial is (x+y)+(z+w); the L partials are summed by a pairwise tree (xor butterfly).
 // The layout depends only on dim — never on batch size — so a (query, row) score is the same
 // bits whichever kernel or batch computes it.  For byte vectors the unit is a 16-byte chunk and
-// the sums are exact int32 (order irrelevant).
+// the sums are exact int32 (order irrelevant).  (L, V) by units (float4s / 16-byte chunks per row, up to
+// 1024 = dim 4096 f32): kCfgLV[cfg_index(units)], osk_internal.h.
 // ---------------------------------------------------------------------------------------------
-struct LaneCfg { int L; int V; };
-OSK_HD LaneCfg lane_cfg(int units) {   // units = float4s (f32) or 16-byte chunks (int8) per row
-    if (units <= 8) return {4, 2};
-    if (units <= 16) return {8, 2};
-    if (units <= 32) return {8, 4};
-    if (units <= 64) return {16, 4};
-    if (units <= 128) return {16, 8};
-    if (units <= 192) return {16, 12};
-    if (units <= 256) return {32, 8};
-    if (units <= 512) return {64, 8};
-    return {64, 16};   // up to 1024 units (dim 4096 f32)
-}
 
 // ---------------------------------------------------------------------------------------------
 // Synthetic corpus: a counter-based generator, identical on host and device (no libm

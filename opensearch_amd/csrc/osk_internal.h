@@ -424,7 +424,11 @@ hipError_t launch_sq6_scan(const Sq8Params& p, int dim, hipStream_t s, hipEvent_
                            hipEvent_t ev_stop = nullptr);
 hipError_t launch_sq8_settle(int cfg, int nq, const SettleParams& p, hipStream_t s);
 
+// The lane configs (osk_common.h, lane layout): cfg_index(units) picks the row of kCfgLV = {L, V} whose
+// L·V units hold a stored row; queries are padded to that many units.
 int cfg_index(int units);
+constexpr int kCfgLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12}, {32, 8}, {64, 8}, {64, 16}};
+inline int cfg_padded_units(int cfg) { return kCfgLV[cfg][0] * kCfgLV[cfg][1]; }
 
 // Process-wide tuning knobs (osk_tune_set).  Every field is an atomic int: a search reads each knob
 // once where it decides on it, and a concurrent osk_tune_set can only switch between valid settings

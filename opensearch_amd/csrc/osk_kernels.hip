@@ -11,7 +11,7 @@
 //   row_norms_*, synth_*, pad_rows   staging helpers.
 //
 // Design notes (full rationale in DESIGN.md):
-//   * A row is scored by L lanes of one wavefront (lane_cfg(dim)); each lane streams V 16-byte
+//   * A row is scored by L lanes of one wavefront (kCfgLV, by dim); each lane streams V 16-byte
 //     units with global_load_dwordx4, so one wave-instruction moves 1 KiB of contiguous-per-row
 //     bytes.  The batch-1 path is HBM-bound by ~30x over the VALU; nothing is staged in LDS.
 //   * Scores never round-trip through HBM: every wavefront keeps a sorted top-k list in lanes
@@ -382,8 +382,6 @@ static const ScanFn kScanI8[9][4] = {
     OSK_I8_ROW(4, 2),  OSK_I8_ROW(8, 2),  OSK_I8_ROW(8, 4),
     OSK_I8_ROW(16, 4), OSK_I8_ROW(16, 8), OSK_I8_ROW(16, 12),
     OSK_I8_ROW(32, 8), OSK_I8_ROW(64, 8), OSK_I8_ROW(64, 16)};
-static const int kCfgLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12},
-                                 {32, 8}, {64, 8}, {64, 16}};
 
 // scan_i8_stream's exact-width configs by 16-byte units (sq8_scan's): ≤4 (4,1) ≤8 (8,1) ≤16 (16,1)
 // ≤32 (16,2) ≤48 (16,3) ≤64 (16,4) ≤128 (32,4) ≤256 (64,4)

@@ -264,7 +264,6 @@ __global__ __launch_bounds__(kBlock) void nest_topk(NestParams p) {
 // dispatch: the scans' lane configs × NQ ∈ {1, kMaxNQ} × {L2, dot-family} × {plain, non-temporal}
 // ------------------------------------------------------------------------------------------------
 using NestFn = void (*)(NestParams);
-constexpr int kLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12}, {32, 8}, {64, 8}, {64, 16}};
 constexpr size_t kLdsMax = 160 * 1024;   // LDS per workgroup on gfx950
 
 #define OSK_NEST_F32_NT(L, V, NT)                                                                               \
@@ -296,11 +295,11 @@ hipError_t launch_nest_scan(int enc, int cfg, const NestParams& p, hipStream_t s
                             hipEvent_t ev_stop) {
     if ((enc != ENC_FLOAT32 && enc != ENC_BYTE) || cfg < 0 || cfg >= 9 || p.sim < 0 || p.sim > 3 || p.q_count < 1 ||
         p.q_count > kMaxNQ || p.n_tiles < 1 || p.n_parents < 1 || p.units < 1 ||
-        p.units > kLV[cfg][0] * kLV[cfg][1] || !p.segs || !p.tiles || !p.nsegs || !p.q || !p.best)
+        p.units > cfg_padded_units(cfg) || !p.segs || !p.tiles || !p.nsegs || !p.q || !p.best)
         return hipErrorInvalidValue;
     const int slot = p.q_count <= 1 ? 0 : 1;
     const int NQ = slot ? kMaxNQ : 1;
-    const int L = kLV[cfg][0], V = kLV[cfg][1];
+    const int L = kCfgLV[cfg][0], V = kCfgLV[cfg][1];
     const bool qreg = NQ * V * 4 <= 64;
     const size_t lds = qreg ? 0 : (size_t)NQ * L * V * 16;
     if (lds + 64 > kLdsMax) return hipErrorInvalidValue;

@@ -113,6 +113,11 @@ struct HostPinned {
 };
 
 inline int units_for(int dim, int enc) { return enc == ENC_FLOAT32 ? (dim + 3) / 4 : (dim + 15) / 16; }
+inline int64_t elem_bytes(int enc) { return enc == ENC_FLOAT32 ? 4 : 1; }
+// A device entry's stream argument: the caller's stream, or (null) the library's own stream of the device.
+inline hipStream_t stream_or_default(void* stream, int device) {
+    return stream ? static_cast<hipStream_t>(stream) : device_stream(device);
+}
 
 }  // namespace osk
 
@@ -174,7 +179,7 @@ struct osk_view {
     osk::DevBuf ws_cand, ws_q, ws_qnorm, ws_qin, ws_keys, ws_counts, ws_accept_ptrs, ws_accept,
         ws_out, ws_visited;
     osk::HostPinned h_stage;
-    osk::HostPinned h_accept_tab;     // osk_view_search's accept pointer table (source of an async copy)
+    osk::HostPinned h_accept_tab;     // upload_accept's pointer table (source of an async copy)
     // batched MFMA path
     bool mfma_ready = false;
     int n_munits = 0;
@@ -265,7 +270,6 @@ struct osk_view {
     hipEvent_t ev_call[2] = {};                 // host entries' per-call device time (tune call_timing)
     double scan_ms = 0.0;
     int64_t scan_calls = 0;
-    const uint64_t* h_accept_ptr = nullptr;   // source of osk_seg_search's one-pointer accept table copy
     // cross-stream ordering of the workspace: the stream of the previous search, and an event recorded
     // on it when a search arrives on another stream (order_after_last)
     hipStream_t last_stream = nullptr;
@@ -309,6 +313,34 @@ struct ViewLease {
     ~ViewLease();
 };
 int32_t lease_view(osk_view* root, ViewLease& out);
+// Host accept bitsets → the view's workspace, on `st` (caller holds v->mu).  `accept` is null or
+// v->segs.size() host bitsets (entries may be null).  *d_accept: the device pointer table, or null when no
+// leaf has a bitset = no filter (the unfiltered scan instances).
+int32_t upload_accept(osk_view* v, const uint64_t* const* accept, hipStream_t st, const uint64_t* const** d_accept);
+// A host search's merged result in one buffer, nq queries of `size` hits:
+// scores f32 | docs i32 | shard i32 | count i32 | total i64 (8-aligned) | max f32.  The coordinator reduce
+// writes it on the device, one copy brings it to a pinned stage, copy_out hands it to the caller's arrays.
+struct MergedOut {
+    size_t b_hits, b_cnt, b_tot, b_max;   // bytes of scores / docs / shard each, count, total, max
+    size_t o_sc, o_doc, o_sh, o_cnt, o_tot, o_max, total_bytes;
+    MergedOut(int nq, int size)
+        : b_hits((size_t)nq * size * 4), b_cnt((size_t)nq * 4), b_tot((size_t)nq * 8), b_max((size_t)nq * 4),
+          o_sc(0), o_doc(o_sc + b_hits), o_sh(o_doc + b_hits), o_cnt(o_sh + b_hits),
+          o_tot((o_cnt + b_cnt + 7) / 8 * 8), o_max(o_tot + b_tot), total_bytes(o_max + b_max) {}
+    struct Ptrs {   // launch_coord_reduce's outputs
+        float* scores;
+        int32_t *docs, *shard, *count;
+        int64_t* total;
+        float* max;
+    };
+    Ptrs at(char* base) const {
+        return {reinterpret_cast<float*>(base + o_sc),    reinterpret_cast<int32_t*>(base + o_doc),
+                reinterpret_cast<int32_t*>(base + o_sh),  reinterpret_cast<int32_t*>(base + o_cnt),
+                reinterpret_cast<int64_t*>(base + o_tot), reinterpret_cast<float*>(base + o_max)};
+    }
+    void copy_out(const char* stage, float* scores, int32_t* docs, int32_t* shard, int32_t* count, int64_t* total,
+                  float* max) const;
+};
 // Per-shard exact top-k on the device (caller holds v->mu; device current).
 int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k, const uint64_t* const* d_accept,
                            uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st);

@@ -401,7 +401,6 @@ __global__ __launch_bounds__(kBlock) void thr_emit_i8(ThrParams p) {
 // dispatch: the scans' lane configs × NQ ∈ {1, kThrNQ} × {L2, dot-family} × {plain, non-temporal}
 // ------------------------------------------------------------------------------------------------
 using ThrFn = void (*)(ThrParams);
-constexpr int kLV[9][2] = {{4, 2}, {8, 2}, {8, 4}, {16, 4}, {16, 8}, {16, 12}, {32, 8}, {64, 8}, {64, 16}};
 constexpr size_t kLdsMax = 160 * 1024;   // LDS per workgroup on gfx950
 
 #define OSK_THR_F32_NT(L, V, NT)                                                                        \
@@ -428,7 +427,7 @@ const ThrFn kThrEmitI8[9] = {thr_emit_i8<4, 2>,  thr_emit_i8<8, 2>,  thr_emit_i8
 bool thr_params_ok(int enc, int cfg, const ThrParams& p) {
     return (enc == ENC_FLOAT32 || enc == ENC_BYTE) && cfg >= 0 && cfg < 9 && p.sim >= 0 && p.sim <= 3 &&
            p.q_count >= 1 && p.q_count <= kThrNQ && p.n_shards >= 1 && p.cap >= 1 &&
-           p.wpw >= 1 && p.n_tiles >= 0 && p.units >= 1 && p.units <= kLV[cfg][0] * kLV[cfg][1] &&
+           p.wpw >= 1 && p.n_tiles >= 0 && p.units >= 1 && p.units <= cfg_padded_units(cfg) &&
            p.segs && p.tiles && p.q && p.min_score && p.mask && p.counts && p.offsets && p.shard_tile_begin &&
            p.out_docs && p.out_scores && p.out_count && p.out_total;
 }
@@ -437,7 +436,7 @@ bool thr_params_ok(int enc, int cfg, const ThrParams& p) {
 
 int thr_words_per_wave(int cfg, int64_t max_tile_rows) {
     if (cfg < 0 || cfg >= 9 || max_tile_rows < 1) return 1;
-    const int64_t R = 64 / kLV[cfg][0];
+    const int64_t R = 64 / kCfgLV[cfg][0];
     const int64_t per_wave = ((max_tile_rows + 4 * R - 1) / (4 * R)) * R;
     return (int)std::min<int64_t>(0x7FFFFFFF, (per_wave + 63) / 64);
 }
@@ -447,7 +446,7 @@ hipError_t launch_thr_scan(int enc, int cfg, const ThrParams& p, hipStream_t s, 
     if (!thr_params_ok(enc, cfg, p) || p.n_tiles < 1) return hipErrorInvalidValue;
     const int slot = p.q_count <= 1 ? 0 : 1;
     const int NQ = slot ? kThrNQ : 1;
-    const int L = kLV[cfg][0], V = kLV[cfg][1];
+    const int L = kCfgLV[cfg][0], V = kCfgLV[cfg][1];
     const bool qreg = NQ * V * 4 <= 64;
     const size_t lds = qreg ? 0 : (size_t)NQ * L * V * 16;
     if (lds > kLdsMax) return hipErrorInvalidValue;

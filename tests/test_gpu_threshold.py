@@ -310,29 +310,53 @@ def test_nan_scores_are_never_hits(enc, dim):
 
 
 # ------------------------------------------------------------------------------------------------
-# filters: ≈ 1 % and 50 %, dense (the compacted walk) and sparse-doc segments
+# filters: ≈ 1 % and 50 %, dense (the compacted walk) and sparse-doc segments, through the segment entry and
+# through a view of the leaves; and a view's mixed accept table — a leaf without a bitset between two with one,
+# at the smallest shape that can go wrong: 130, 64 and 1 rows, the first leaf's 200 docs no multiple of 64
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "sparse"])
-@pytest.mark.parametrize("pct", [1, 50])
-def test_filtered(pct, sparse):
-    dim, sim, n = 96, SIM.EUCLIDEAN, 4097
-    rows = synth(n, dim, 700)
+# a case: dim, similarity and, per leaf, (rows, max_doc when its docs are sparse, accepted % of its docs or None
+# for a leaf without a bitset)
+FILTERED = [pytest.param(96, SIM.EUCLIDEAN, [(4097, 3 * 4097 if sparse else None, pct)], id=f"{pct}-{name}")
+            for name, sparse in (("dense", False), ("sparse", True)) for pct in (1, 50)]
+FILTERED.append(pytest.param(8, SIM.COSINE, [(130, 200, 50), (64, None, None), (1, None, 100)], id="mixed-view"))
+
+
+@pytest.mark.parametrize("dim,sim,leaves", FILTERED)
+def test_filtered(dim, sim, leaves):
     q = synth(1, dim, 701)[0]
-    rng = np.random.default_rng(pct)
-    o2d = np.sort(rng.choice(3 * n, n, replace=False)).astype(np.int32) if sparse else None
-    max_doc = 3 * n if sparse else n
-    acc = rng.random(max_doc) < pct / 100
-    r = LU.GpuFlatVectorsReader("v", rows, sim, F32, ord_to_doc=o2d, max_doc=max_doc)
+    rows, o2d, acc, bases, readers = [], [], [], [], []
+    ds = None
     try:
-        scored = all_scores(("filt", pct, sparse), rows, q, sim, o2d, acc)
-        n_acc = int(acc[o2d].sum()) if sparse else int(acc.sum())
-        assert scored[2] == n_acc > 0
-        for m in (NEG_INF, jth_best(scored, 5), jth_best(scored, max(1, n_acc // 2))):
-            d, s, c, t, v = r.search_threshold(q, m, LU.bits_from_bool(acc), n)
-            assert_hits((d[0], s[0], c[0], t[0]), reference(scored, m), n, (pct, sparse, m))
-            assert v[0] == n_acc
+        for i, (n, sparse_max_doc, pct) in enumerate(leaves):
+            rng = np.random.default_rng(pct or 0)
+            max_doc = sparse_max_doc or n
+            rows.append(synth(n, dim, 700 + i))
+            o2d.append(np.sort(rng.choice(max_doc, n, replace=False)).astype(np.int32) if sparse_max_doc else None)
+            acc.append(None if pct is None else rng.random(max_doc) < pct / 100)
+            bases.append(sum(r.max_doc for r in readers))
+            readers.append(LU.GpuFlatVectorsReader("v", rows[i], sim, F32, ord_to_doc=o2d[i], max_doc=max_doc))
+        ds = LU.DeviceShardSet([[LU.LeafReaderContext(i, bases[i], r) for i, r in enumerate(readers)]], [0])
+        scored = [all_scores(("filt", dim, i) + leaves[i], rows[i], q, sim, o2d[i], acc[i]) for i in range(len(leaves))]
+        n_acc = [len(rows[i]) if acc[i] is None else int((acc[i] if o2d[i] is None else acc[i][o2d[i]]).sum())
+                 for i in range(len(leaves))]
+        assert all(scored[i][2] == n_acc[i] > 0 for i in range(len(leaves)))
+        whole = (None, np.concatenate([s[1] for s in scored]))
+        cap = sum(len(r) for r in rows)
+        for m in (NEG_INF, jth_best(whole, 5), jth_best(whole, max(1, sum(n_acc) // 2))):
+            for i, r in enumerate(readers):
+                bits = None if acc[i] is None else LU.bits_from_bool(acc[i])
+                d, s, c, t, v = r.search_threshold(q, m, bits, cap)
+                assert_hits((d[0], s[0], c[0], t[0]), reference(scored[i], m), cap, (leaves[i], m))
+                assert v[0] == n_acc[i]
+            want = [reference(scored[i], m, bases[i]) for i in range(len(leaves))]
+            d, s, c, t = ds.search_threshold(q, m, acc, cap)
+            assert_hits((d[0, 0], s[0, 0], c[0, 0], t[0, 0]),
+                        (np.concatenate([w[0] for w in want]), np.concatenate([w[1] for w in want])), cap, ("view", m))
     finally:
-        r.close()
+        if ds is not None:
+            ds.close()
+        for r in readers:
+            r.close()
 
 
 # ------------------------------------------------------------------------------------------------
