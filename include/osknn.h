@@ -284,9 +284,14 @@ int32_t osk_view_scan_time(osk_view* view, double* total_ms, int64_t* calls);
  *   "sq8_wide_quarter_rows"  rows per wide quarter (default 0 = auto, ≤ 16,384; at the view's first wide batch)
  *   "sq8_scan_deep"   0|1 single-query sq8_scan over ≤ 256 dims with 8 row groups in flight per wave
  *                     (default 0: measured slower)
+ *   "thr_sq8"         0|1 similarity-threshold searches of float32 views read the int8 prefilter copy first
+ *                     (default 1; needs "sq8" = 1 and no row outside the certificate's range): rows whose certified
+ *                     score interval clears min_score on either side are decided there, the others are re-scored
+ *                     exactly from the float32 rows.  0 = the float32 scan.  Same results.
  * The testing build (libosknn_testing.so) also accepts "sq8_mfma_ablate", "mfma_ablate" (A/B timing,
- * results wrong), "sq8_force_fallback" (every prefilter list re-scanned exactly) and "settle_trace";
- * the shipped library returns OSK_ERR_UNSUPPORTED for them. */
+ * results wrong), "sq8_force_fallback" (every prefilter list re-scanned exactly), "settle_trace" and
+ * "thr_sq8_all_maybe" (the int8 first pass of a threshold search decides nothing: every accepted candidate
+ * row is re-scored exactly; results unchanged); the shipped library returns OSK_ERR_UNSUPPORTED for them. */
 int32_t osk_tune_set(const char* key, int64_t value);
 
 /* Batched-path counters of a view: searches that took the MFMA path, and queries among them whose
@@ -298,7 +303,9 @@ int32_t osk_view_stats(osk_view* view, int64_t* batched_calls, int64_t* fallback
  * "sq8_fallback_queries" (queries where some tile's candidate
  * list overflowed past the certificate and the tile was re-scanned exactly), "sq8_exact_tiles"
  * (such tiles), "sq8_rescored_rows" (rows re-scored exactly, all calls), "select_calls" (searches
- * on the select path, k > 12), "threshold_calls" (similarity-threshold searches), "nested_calls" (nested k-NN searches),"host_slots" (workspace slots the host entries have leased: 1 + replicas),
+ * on the select path, k > 12), "threshold_calls" (similarity-threshold searches), "threshold_sq8_calls" (those
+ * that took the int8 first pass, knob "thr_sq8"), "threshold_sq8_settled_rows" (rows it left undecided and the
+ * settle re-scored exactly, all calls), "nested_calls" (nested k-NN searches), "host_slots" (workspace slots the host entries have leased: 1 + replicas),
  * "host_batches" / "host_batched_requests" (opportunistic batching of concurrent host calls).  The
  * search counters sum over the view and the replica slots its host entries leased.  osk_view_profile /
  * osk_view_scan_time time the device-entry calls on this view object only (per-call host timing:

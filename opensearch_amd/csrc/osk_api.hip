@@ -346,6 +346,8 @@ int32_t osk_tune_set(const char* key, int64_t value) {
         {"sq8_mfma_ring", &g_tuning.sq8_mfma_ring, -1, 8, false},
         {"i8_stream", &g_tuning.i8_stream, 0, 1, false},
         {"call_timing", &g_tuning.call_timing, 0, 1, false},
+        {"thr_sq8", &g_tuning.thr_sq8, 0, 1, false},
+        {"thr_sq8_all_maybe", &g_tuning.thr_sq8_all_maybe, 0, 1, true},
         {"sq8_mfma_ablate", &g_tuning.sq8_mfma_ablate, 0, 1023, true},   // (also sq6_scan's: 1 no re-bound, 2 no floor,
                                                                           // 16 loads only; sq6_rebound's: 256 no list work)
         {"sq8_force_fallback", &g_tuning.sq8_force_fallback, 0, 1, true},
@@ -2293,11 +2295,43 @@ int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const 
     OSK_HIP(v->ws_thr_mask.reserve(sizeof(uint64_t) * kThrNQ * waves * wpw));
     OSK_HIP(v->ws_thr_wcounts.reserve(sizeof(int32_t) * kThrNQ * waves));
     OSK_HIP(v->ws_thr_offsets.reserve(sizeof(int64_t) * kThrNQ * waves));
-    OSK_HIP(launch_prep_queries(d_queries, v->dim * elem_bytes(v->enc), nq, v->ws_q.p, UP, nq_pad, st));
+    // float32 views whose int8 copy certifies (no row outside the certificate's range) take the int8 first
+    // pass: thr_scan_sq8 settles every row whose interval clears min_score on ¼ of the bytes, thr_settle_f32
+    // re-scores the rest exactly.  Every other view, and every byte field, keeps the fp32 / byte scan.
+    bool use8 = v->enc == ENC_FLOAT32 && v->n_tiles > 0 && g_tuning.thr_sq8.load(std::memory_order_relaxed) &&
+                g_tuning.sq8 && !(v->sq8_ready && !v->sq8_range_ok);
+    if (use8) {
+        if ((rc = ensure_sq8(v, st)) != OSK_OK) return rc;
+        use8 = v->sq8_range_ok;
+    }
+    if (use8) {   // the select path's fused prep: padded fp32 queries, |q|², int8 codes, bound terms, flags
+        const int u8 = v->units8;
+        OSK_HIP(v->ws_thr_maybe.reserve(sizeof(uint64_t) * kThrNQ * waves * wpw));
+        OSK_HIP(v->ws_qnorm.reserve(sizeof(float) * nq_pad));
+        OSK_HIP(v->ws_q8.reserve((size_t)nq_pad * u8 * 16));
+        OSK_HIP(v->ws_qc.reserve(sizeof(float4) * nq_pad));
+        OSK_HIP(v->ws_flags.reserve(sizeof(int) * nq_pad));
+        OSK_HIP(launch_sq8_prep(v->cfg, static_cast<const float*>(d_queries), v->dim, nq, nq_pad, UP, u8,
+                                v->ws_q.as<float4>(), v->ws_qnorm.as<float>(), v->ws_q8.p, v->ws_qc.as<float4>(),
+                                v->ws_flags.as<int>(), st));
+    } else {
+        OSK_HIP(launch_prep_queries(d_queries, v->dim * elem_bytes(v->enc), nq, v->ws_q.p, UP, nq_pad, st));
+    }
     if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
     if ((rc = profile_sample(v, st, false)) != OSK_OK) return rc;
 
     ThrParams p{};
+    if (use8) {
+        p.maybe = v->ws_thr_maybe.as<uint64_t>();
+        p.rows8 = v->d_sq8_rows.as<const int4*>();
+        p.aux = v->d_sq8_aux.as<const float4*>();
+        p.settled = v->d_counters.as<unsigned long long>() + 22;
+        p.gam = v->sq8_gam;
+        p.g2 = v->sq8_g2;
+        p.units8 = v->units8;
+        p.wave_R = 64 / kCfgLV[v->cfg][0];
+        p.all_maybe = g_tuning.thr_sq8_all_maybe.load(std::memory_order_relaxed);
+    }
     p.segs = v->d_segs.as<SegDev>();
     p.tiles = v->d_tiles.as<TileDev>();
     p.accept = d_accept;
@@ -2324,14 +2358,25 @@ int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const 
         p.min_score = d_min_scores + q0;
         if (v->n_tiles > 0) {   // (nothing staged: thr_offsets alone writes zero hits for every shard)
             OSK_HIP(hipMemsetAsync(p.mask, 0, sizeof(uint64_t) * p.q_count * waves * wpw, st));
-            OSK_HIP(launch_thr_scan(v->enc, v->cfg, p, st, launch_ev_start(v, q0),
-                                    v->profile && q0 + kThrNQ >= nq ? v->ev1 : nullptr));
+            hipEvent_t ev_stop = v->profile && q0 + kThrNQ >= nq ? v->ev1 : nullptr;
+            if (use8) {
+                OSK_HIP(hipMemsetAsync(p.maybe, 0, sizeof(uint64_t) * p.q_count * waves * wpw, st));
+                p.q8 = v->ws_q8.as<int4>() + (size_t)q0 * v->units8;
+                p.qc = v->ws_qc.as<float4>() + q0;
+                p.qnorm = v->ws_qnorm.as<float>() + q0;
+                p.qflags = v->ws_flags.as<int>() + q0;
+                OSK_HIP(launch_thr_scan_sq8(v->cfg, p, st, launch_ev_start(v, q0), ev_stop));
+                OSK_HIP(launch_thr_settle(v->cfg, p, st));
+            } else {
+                OSK_HIP(launch_thr_scan(v->enc, v->cfg, p, st, launch_ev_start(v, q0), ev_stop));
+            }
         }
         OSK_HIP(launch_thr_offsets(p, st));
         if (v->n_tiles > 0) OSK_HIP(launch_thr_emit(v->enc, v->cfg, p, st));
     }
     if (v->n_tiles > 0 && (rc = profile_end(v, st, false)) != OSK_OK) return rc;
     v->thr_calls += 1;
+    v->thr_sq8_calls += use8 ? 1 : 0;
     return OSK_OK;
 }
 
@@ -2747,9 +2792,11 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
                      n == "sq6_rebound_gathered_rows" || n == "sq6_rebound_passes" ||
                      n == "sq6_rebound_max_wg_cycles" || n == "sq8_rows_total_cycles" || n == "sq8_rows_setup_cycles" ||
                      n == "sq8_rows_quarter_end_cycles" || n == "sq8_rows_first_wait_cycles" ||
-                     n == "sq8_rows_setup_barrier_cycles" || n == "sq8_rows_setup_fragment_cycles";
+                     n == "sq8_rows_setup_barrier_cycles" || n == "sq8_rows_setup_fragment_cycles" ||
+                     n == "threshold_sq8_settled_rows";
     OSK_REQUIRE(dev || n == "mfma_calls" || n == "mfma_fallback_queries" || n == "sq8_calls" || n == "sq6_calls" ||
-                    n == "select_calls" || n == "sq8_wide_calls" || n == "threshold_calls" || n == "nested_calls",
+                    n == "select_calls" || n == "sq8_wide_calls" || n == "threshold_calls" || n == "nested_calls" ||
+                    n == "threshold_sq8_calls",
                 "unknown counter: " + n);
     // summed over the view and the replicas its host entries leased
     int64_t sum = 0;
@@ -2774,12 +2821,14 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
                              // flush, next constants), the waits for each quarter's first group (testing build)
                              : n == "sq8_rows_total_cycles" ? c[16] : n == "sq8_rows_setup_cycles" ? c[17]
                              : n == "sq8_rows_quarter_end_cycles" ? c[18] : n == "sq8_rows_first_wait_cycles" ? c[19]
-                             : n == "sq8_rows_setup_barrier_cycles" ? c[20] : c[21]);
+                             : n == "sq8_rows_setup_barrier_cycles" ? c[20]
+                             : n == "sq8_rows_setup_fragment_cycles" ? c[21]
+                             : c[22]);   // [22]: rows thr_settle_f32 re-scored (threshold_sq8_settled_rows)
         } else {
             sum += n == "mfma_calls" ? s->mfma_calls : n == "mfma_fallback_queries" ? s->mfma_fallback_queries
                  : n == "sq8_calls" ? s->sq8_calls : n == "sq6_calls" ? s->sq6_calls
                  : n == "sq8_wide_calls" ? s->sq8w_calls : n == "threshold_calls" ? s->thr_calls
-                 : n == "nested_calls" ? s->nest_calls : s->sel_calls;
+                 : n == "threshold_sq8_calls" ? s->thr_sq8_calls : n == "nested_calls" ? s->nest_calls : s->sel_calls;
         }
     }
     *value = sum;

@@ -104,6 +104,46 @@ __device__ __forceinline__ bool sq8_pass(int sim, float lo, float hi, float tq, 
     return !(hi < tq);
 }
 
+// COSINE bounds without Java's double transform.  LB/UB only have to bracket the exact score: with
+// c = d/√(qn·xn) evaluated in fp32 (two v_rsq, two products: ≤ 2^-20·|c| from the real quotient) and
+// Java's (float)(d / sqrt((double)qn·xn)) then (1 + c)/2 within 2^-23 of the real value, an absolute
+// slack of 2^-17·max(1, |c|) keeps ub ≥ score(hi) ≥ the exact score ≥ score(lo) ≥ lb.  Degenerate norms
+// (0, inf, NaN) take the exact transform.
+__device__ __forceinline__ void cos_bounds_fast(float lo, float hi, float qn, float xn, float& lb, float& ub) {
+    const float r = rsqrtf(qn) * rsqrtf(xn);
+    const float ch = hi * r, cl = lo * r;
+    ub = fmaf(0.5f, ch, 0.5f) + 0x1p-17f * fmaxf(1.0f, fabsf(ch));
+    lb = fmaxf(0.0f, fmaf(0.5f, cl, 0.5f) - 0x1p-17f * fmaxf(1.0f, fabsf(cl)));
+}
+
+// The certified score interval [lb, ub] of one (row, query) from the row's int8 dot `acc`: sq8_bounds'
+// raw interval through the similarity's score transform.  Shared by the select path's writer (sel_bounds)
+// and the threshold search's first pass (thr_scan_sq8), so both trust one arithmetic.  Every lane of the
+// wave must call it (one ballot).  qnd / xnd: the device-order |q|², |x|² (COSINE; 0 otherwise, and for
+// rows that are not valid).  FAST: COSINE through cos_bounds_fast unless a valid row of this wave step has
+// a degenerate norm.  qopen (wave-uniform): the query is outside the certificate's range, every score is in
+// [0, +inf].  Returns whether the row is a candidate: valid and neither bound NaN (COSINE with a zero
+// query or row: its exact score is NaN too, and a NaN is never a hit).
+template <bool FAST>
+__device__ __forceinline__ bool sq8_score_interval(int sim, int acc, float4 ax, float4 qc, float gam, float g2,
+                                                   float qnd, float xnd, bool valid, bool qopen, float& lb,
+                                                   float& ub) {
+    float lo, hi;
+    sq8_bounds(sim, (float)acc, ax, qc, gam, g2, lo, hi);
+    const bool degen = !(qnd > 0.0f && qnd < __builtin_inff() && xnd > 0.0f && xnd < __builtin_inff());
+    if (FAST && sim == SIM_COSINE && !__ballot(valid && degen)) {   // (wave-uniform)
+        cos_bounds_fast(lo, hi, qnd, xnd, lb, ub);
+    } else {
+        ub = sim == SIM_EUCLIDEAN ? score_f32_l2(lo) : score_f32(sim, hi, qnd, xnd);
+        lb = sim == SIM_EUCLIDEAN ? score_f32_l2(hi) : score_f32(sim, lo, qnd, xnd);
+    }
+    if (qopen) {   // every row a candidate, re-scored exactly
+        lb = 0.0f;
+        ub = __builtin_inff();
+    }
+    return valid && lb == lb && ub == ub;
+}
+
 // A workgroup's visited rows, added with ONE global atomic per workgroup: per-wave atomics on a
 // segment's counter queue at L2 behind each other and hold the kernel's last waves (every thread of the
 // workgroup must call this: it has barriers).

@@ -486,6 +486,9 @@ struct Tuning {
     std::atomic<int> sq8_wide_force{0};   // (tests) the wide kernel for every eligible batch, whatever the model says
     std::atomic<int> sq8_wide_phase{8};   // the wide kernel's first pass covers 1/this of the quarters, whose lists
                                           // raise the floors of the rest (0: one pass)
+    std::atomic<int> thr_sq8{1};          // threshold search of float32 views: the certified int8 first pass
+                                          // (thr_scan_sq8 + thr_settle_f32) instead of the fp32 scan (same results)
+    std::atomic<int> thr_sq8_all_maybe{0};    // TESTING. thr_scan_sq8 classifies every accepted candidate row as maybe
     std::atomic<int> sq8_force_fallback{0};   // TESTING. tests: every list of a prefiltered search is re-scanned exactly
     std::atomic<int> settle_trace{0};     // TESTING. A/B only: record settle phase timestamps (debug copy "settle_trace")
     std::atomic<int> mfma_ablate{0};      // TESTING. A/B only: 1 skip the epilogue, 2 skip query staging, 4 skip corpus staging,
@@ -528,11 +531,30 @@ struct ThrParams {
     int sim;
     int dim;
     int cap;
+    // the certified int8 first pass (thr_scan_sq8 → thr_settle_f32; float32 views, null / 0 otherwise)
+    uint64_t* maybe;                 // mask's layout: rows whose interval straddles min_score (zeroed with mask)
+    const int4* const* rows8;        // [n_segs] the int8 prefilter copy: codes, units8 int4 per row
+    const float4* const* aux;        // [n_segs] its bound terms, one float4 per row
+    const int4* q8;                  // this pass's sq8_prep outputs: codes [q_count][units8],
+    const float4* qc;                // bound terms [q_count],
+    const float* qnorm;              // device-order |q|² [q_count],
+    const int* qflags;               // flags [q_count] (kQueryOutOfRange)
+    unsigned long long* settled;     // [1] rows thr_settle_f32 re-scored (the view's device counter)
+    float gam, g2;                   // rounding bounds of the fp32 device order (ensure_sq8)
+    int units8;
+    int wave_R;                      // rows per wave step of the view's FLOAT32 lane config: a tile is split
+                                     // among its waves by it (thr_wave_range), whatever config walks the rows
+    int all_maybe;                   // TESTING: every accepted candidate row is a maybe
 };
 int thr_words_per_wave(int cfg, int64_t max_tile_rows);
 // Every launcher checks its grid, LDS and arguments and returns hipErrorInvalidValue instead of launching.
 hipError_t launch_thr_scan(int enc, int cfg, const ThrParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr);
+// float32 views with the int8 copy: the first pass on it (sure hits → mask and counts, straddling rows →
+// maybe), then the exact re-score of the maybes (adds their hits to mask and counts)
+hipError_t launch_thr_scan_sq8(int cfg, const ThrParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
+                               hipEvent_t ev_stop = nullptr);
+hipError_t launch_thr_settle(int cfg, const ThrParams& p, hipStream_t s);
 hipError_t launch_thr_offsets(const ThrParams& p, hipStream_t s);
 hipError_t launch_thr_emit(int enc, int cfg, const ThrParams& p, hipStream_t s);
 // ---- nested k-NN (osk_nested.hip): the best accepted child of each parent, then the k best parents ----

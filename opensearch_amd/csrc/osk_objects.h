@@ -239,7 +239,8 @@ struct osk_view {
     // pass (≤ kThrNQ queries), the thresholds, and the host entries' device outputs
     int64_t max_tile_rows = 0;             // the largest tile's rows (sizes the mask: thr_words_per_wave)
     osk::DevBuf ws_thr_mask, ws_thr_wcounts, ws_thr_offsets, ws_thr_min, ws_thr_out;
-    int64_t thr_calls = 0;
+    osk::DevBuf ws_thr_maybe;              // the int8 first pass's second mask: rows to re-score exactly
+    int64_t thr_calls = 0, thr_sq8_calls = 0;   // threshold searches; those that took the int8 first pass
     // nested k-NN (osk_nested.hip), built at the first nested search or by osk_view_warm (ensure_nested): each
     // segment's row→parent table and parent-slot base (a shard's parent slots are contiguous), the parent
     // tiles and their shard ranges; the per-pass best-child keys and the parent tiles' candidates

@@ -111,5 +111,13 @@ __device__ __forceinline__ void thr_wave_range(const TileDev& tile, int wave, in
     wb = min(tile.row_begin + wave * per_wave, tile.row_end);
     we = min(wb + per_wave, tile.row_end);
 }
+// ...the same split for a kernel that walks the rows in another lane config than the one whose R splits
+// the tile (thr_scan_sq8: the int8 configs' R differs from the float32 config's)
+__device__ __forceinline__ void thr_wave_range_rt(const TileDev& tile, int wave, int R, int64_t& wb, int64_t& we) {
+    const int64_t rows = tile.row_end - tile.row_begin;
+    const int64_t per_wave = ((rows + 4 * R - 1) / (4 * R)) * R;
+    wb = min(tile.row_begin + wave * per_wave, tile.row_end);
+    we = min(wb + per_wave, tile.row_end);
+}
 
 }  // namespace osk

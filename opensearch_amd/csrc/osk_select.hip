@@ -171,21 +171,9 @@ __global__ __launch_bounds__(kSelThreads) void sel_keys_i8(SelParams p) {
     if (p.visited) add_visited_wg(&p.visited[tile.seg], (uint32_t)nvis);
 }
 
-// COSINE bounds without Java's double transform.  LB/UB only have to bracket the exact score: with
-// c = d/√(qn·xn) evaluated in fp32 (two v_rsq, two products: ≤ 2^-20·|c| from the real quotient) and
-// Java's (float)(d / sqrt((double)qn·xn)) then (1 + c)/2 within 2^-23 of the real value, an absolute
-// slack of 2^-17·max(1, |c|) keeps ub ≥ score(hi) ≥ the exact score ≥ score(lo) ≥ lb.  Degenerate norms
-// (0, inf, NaN) take the exact transform.
-__device__ __forceinline__ void cos_bounds_fast(float lo, float hi, float qn, float xn, float& lb, float& ub) {
-    const float r = rsqrtf(qn) * rsqrtf(xn);
-    const float ch = hi * r, cl = lo * r;
-    ub = fmaf(0.5f, ch, 0.5f) + 0x1p-17f * fmaxf(1.0f, fabsf(ch));
-    lb = fmaxf(0.0f, fmaf(0.5f, cl, 0.5f) - 0x1p-17f * fmaxf(1.0f, fabsf(cl)));
-}
-
-// bounds mode: the int8 prefilter copy's certified [lb, ub] score interval per row (sq8_scan's bound),
-// U row groups loaded before any is reduced (≈ U·V KiB in flight per wave, as sq8_scan).  FAST: COSINE
-// through cos_bounds_fast instead of Java's double transform.
+// bounds mode: the int8 prefilter copy's certified [lb, ub] score interval per row (sq8_scan's bound,
+// osk_device.h sq8_score_interval), U row groups loaded before any is reduced (≈ U·V KiB in flight per
+// wave, as sq8_scan).  FAST: COSINE through cos_bounds_fast instead of Java's double transform.
 template <int L, int V, bool FILT, int U, bool FAST>
 __global__ __launch_bounds__(kSelThreads) void sel_bounds(SelParams p) {
     constexpr int R = 64 / L;
@@ -251,26 +239,14 @@ __global__ __launch_bounds__(kSelThreads) void sel_bounds(SelParams p) {
                 acc = __builtin_amdgcn_sdot4(xv[u][j].w, qf[j].w, acc, false);
             }
             acc = lane_sum<L>(acc);
-            float lo, hi;
-            sq8_bounds(sim, (float)acc, ax[u], qc, p.gam, p.g2, lo, hi);
             const float xnd = (sim == SIM_COSINE && valid[u]) ? seg.xnorm_f[row[u]] : 0.0f;
             float ub, lb;
-            const bool degen = !(qnd > 0.0f && qnd < __builtin_inff() && xnd > 0.0f && xnd < __builtin_inff());
-            if (FAST && sim == SIM_COSINE && !__ballot(valid[u] && degen)) {   // (wave-uniform)
-                cos_bounds_fast(lo, hi, qnd, xnd, lb, ub);
-            } else {
-                ub = sim == SIM_EUCLIDEAN ? score_f32_l2(lo) : score_f32(sim, hi, qnd, xnd);
-                lb = sim == SIM_EUCLIDEAN ? score_f32_l2(hi) : score_f32(sim, lo, qnd, xnd);
-            }
-            if (qopen) {   // (wave-uniform) every score is in [0, +inf]: every row a candidate, re-scored exactly
-                lb = 0.0f;
-                ub = __builtin_inff();
-            }
-            nvis += __popcll(__ballot(t == 0 && valid[u]));
             // every real score is ≥ 0, whose sortable form is ≥ 2^31: 0 = no row.  A NaN bound (COSINE with a zero
             // query or row: its exact score is NaN too) is no row either — a NaN is never a hit (make_key), and
             // the select must not count it among the k it keeps
-            const bool cand = valid[u] && lb == lb && ub == ub;
+            const bool cand =
+                sq8_score_interval<FAST>(sim, acc, ax[u], qc, p.gam, p.g2, qnd, xnd, valid[u], qopen, lb, ub);
+            nvis += __popcll(__ballot(t == 0 && valid[u]));
             lbv[u] = cand ? float_to_sortable(lb) : 0u;
             ubv[u] = cand ? float_to_sortable(ub) : 0u;
         }

@@ -8,6 +8,10 @@
 //                                replaced by `hit = valid && score >= min_score` → one ballot per row
 //                                group → 64-bit mask words + a per-(query, tile, wave) hit count.
 //                                No score round-trips through HBM.
+//   thr_scan_sq8 + thr_settle_f32  float32 views whose int8 prefilter copy certifies (tune thr_sq8): the same
+//                                mask and counts from ¼ of the bytes — the int8 copy's certified score
+//                                interval decides every row it can (sure hit / sure miss), the rows whose
+//                                interval straddles min_score go to a second mask and are re-scored exactly.
 //   thr_offsets                  per (query, shard): exclusive prefix sum of the wave counts in tile
 //                                order (= segment by doc_base, then row, order) → each wave's output
 //                                offset, the shard's exact total, min(total, cap), and the unused
@@ -264,6 +268,282 @@ __global__ __launch_bounds__(kBlock) void thr_scan_i8(ThrParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// scan, float32 views, certified int8 first pass: the select path's bounds writer (sel_bounds: int8 lane
+// configs by 16-byte units, U row groups loaded — unconditional, clamped, masked — before any is reduced,
+// non-temporal int4 loads, sdot4, one float4 of bound terms per row) with the records replaced by a
+// classification of each accepted row against min_score:
+//   sure   cand && lb >= ms                    (score ≥ lb ≥ ms)   → the hit mask and the wave's count
+//   maybe  cand && !(lb >= ms) && !(ub < ms)   → the maybe mask: thr_settle_f32 re-scores the row exactly
+// and everything else no hit (!cand: a NaN bound, whose exact score is NaN too).  Both comparisons are false
+// for a NaN ms, which would make every row a maybe: a NaN ms is tested once per query and makes every row
+// a miss.  An out-of-range query's interval is [0, +inf]: every row a maybe (exact, and slow).
+//
+// Wave split: the masks are addressed per wave (wpw words, bit = row − the wave's first row) and the settle
+// and the emit find a wave's rows with thr_wave_range<R> of the view's FLOAT32 lane config.  This kernel's
+// R8 = 64 / L differs, so it takes the fp32 config's R (p.wave_R) for the split and steps by R8·U rows
+// inside the wave's range: R8·U divides 64 and the steps start at multiples of it from the wave's first
+// row, so a step's rows lie in one word, and no two waves ever store the same word.
+// ------------------------------------------------------------------------------------------------
+template <int L, int V, int NQ, bool FILT>
+__global__ __launch_bounds__(kBlock) void thr_scan_sq8(ThrParams p) {
+    constexpr int R = 64 / L;
+    constexpr int U = 2;
+    constexpr int S = R * U;   // rows per step
+    static_assert(64 % S == 0 && U * NQ * 2 <= 32, "a step's rows in one word, its classes in one dword");
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t = lane & (L - 1), g = lane / L;
+    const TileDev tile = p.tiles[blockIdx.x];
+    const SegDev seg = p.segs[tile.seg];
+    const uint64_t* abits = (FILT && p.accept) ? p.accept[tile.seg] : nullptr;
+    const int4* __restrict__ X = p.rows8[tile.seg];
+    const float4* __restrict__ AX = p.aux[tile.seg];
+    const int u8 = p.units8, sim = p.sim;
+
+    int4 qf[NQ][V];
+    float4 qc[NQ];
+    float qnd[NQ], ms[NQ];
+    bool qopen[NQ], live[NQ];
+#pragma unroll
+    for (int b = 0; b < NQ; ++b) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const int f = t + j * L;
+            const int msk = f < u8 ? -1 : 0;
+            const int4 v = p.q8[(size_t)b * u8 + (f < u8 ? f : 0)];
+            qf[b][j] = make_int4(v.x & msk, v.y & msk, v.z & msk, v.w & msk);
+        }
+        const bool inq = b < p.q_count;
+        qc[b] = p.qc[b];
+        qnd[b] = sim == SIM_COSINE ? p.qnorm[b] : 0.0f;
+        qopen[b] = inq && (p.qflags[b] & kQueryOutOfRange) != 0;
+        ms[b] = inq ? p.min_score[b] : __builtin_nanf("");
+        live[b] = ms[b] == ms[b];   // (wave-uniform) a NaN threshold: no row is a hit, none needs a re-score
+    }
+
+    int64_t wb, we;
+    thr_wave_range_rt(tile, wave, p.wave_R, wb, we);
+    const size_t qstride = (size_t)p.n_tiles * 4 * p.wpw;
+    const size_t wi = (size_t)blockIdx.x * 4 + wave;
+    uint64_t* hw = p.mask + wi * p.wpw;
+    uint64_t* mw = p.maybe + wi * p.wpw;
+
+    ThrMask<NQ> hm, mm;
+    hm.init();
+    mm.init();
+    uint32_t nvis = 0;
+
+    // one row group's classes against the NQ thresholds: bit 2b sure, bit 2b + 1 maybe (every lane calls it)
+    auto classify = [&](const int4 (&x)[V], float4 axr, float xnd, bool valid) -> uint32_t {
+        uint32_t cls = 0u;
+#pragma unroll
+        for (int b = 0; b < NQ; ++b) {
+            int acc = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                acc = __builtin_amdgcn_sdot4(x[j].x, qf[b][j].x, acc, false);
+                acc = __builtin_amdgcn_sdot4(x[j].y, qf[b][j].y, acc, false);
+                acc = __builtin_amdgcn_sdot4(x[j].z, qf[b][j].z, acc, false);
+                acc = __builtin_amdgcn_sdot4(x[j].w, qf[b][j].w, acc, false);
+            }
+            acc = lane_sum<L>(acc);
+            float lb, ub;
+            const bool cand =
+                sq8_score_interval<true>(sim, acc, axr, qc[b], p.gam, p.g2, qnd[b], xnd, valid, qopen[b], lb, ub);
+            // An out-of-range query's [0, +inf] is no certificate — its exact score may even be NaN — so none
+            // of its rows is sure, whatever ms: every one is re-scored.  Nor is a COSINE row sure when |q|² or
+            // |x|² is 0 (or not finite): the exact score is NaN, never a hit, while the transform of ±x/0
+            // gives the interval [0, +inf], not NaN.
+            const bool degen = sim == SIM_COSINE && !(qnd[b] > 0.0f && qnd[b] < __builtin_inff() && xnd > 0.0f &&
+                                                      xnd < __builtin_inff());
+            bool sure = cand && !qopen[b] && !degen && lb >= ms[b];
+            bool maybe = cand && live[b] && !sure && !(ub < ms[b]);
+            if (p.all_maybe) {   // (testing build) the settle decides every candidate row
+                sure = false;
+                maybe = cand;
+            }
+            cls |= ((sure ? 1u : 0u) | (maybe ? 2u : 0u)) << (2 * b);
+        }
+        return cls;
+    };
+
+    if (FILT && abits && !seg.ord_to_doc) {
+        // a filter on a dense segment: walk_rows' compaction, as thr_scan_f32 — only accepted rows are read
+        // (at 1 % selectivity 1 % of the bytes), R per step out of one 64-row window that starts at a multiple
+        // of 64 from the wave's first row, each row setting its own bit
+        walk_rows<R>(wb, we, abits, nullptr, lane, g, [&](const int64_t row, bool valid, bool) {
+            const int64_t rc = valid ? row : wb;   // (a lane group past the window's accepted rows)
+            const int4* xr = X + rc * u8;
+            int4 x[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const int f = t + j * L;
+                const int4 xl = load_i4_nt(xr + (f < u8 ? f : 0));
+                const int m = (valid && f < u8) ? -1 : 0;
+                x[j] = make_int4(xl.x & m, xl.y & m, xl.z & m, xl.w & m);
+            }
+            const float4 axr = AX[rc];
+            const float xnd = (sim == SIM_COSINE && valid) ? seg.xnorm_f[rc] : 0.0f;
+            nvis += __popcll(__ballot(t == 0 && valid));
+            const int rel = (int)(rc - wb);
+            const int widx = __builtin_amdgcn_readfirstlane(rel) >> 6;   // lane 0's group is always a valid row
+            if (widx != hm.idx) {
+                hm.flush(hw, qstride, p.wpw, p.q_count, lane);
+                mm.flush(mw, qstride, p.wpw, p.q_count, lane);
+                hm.idx = mm.idx = widx;
+            }
+            const uint32_t cls = classify(x, axr, xnd, valid);
+#pragma unroll
+            for (int b = 0; b < NQ; ++b) {
+                hm.bits[b] |= thr_step_bits<L>(((cls >> (2 * b)) & 1u) != 0u, false, rel, lane, t);
+                mm.bits[b] |= thr_step_bits<L>(((cls >> (2 * b + 1)) & 1u) != 0u, false, rel, lane, t);
+            }
+        });
+    } else {
+        for (int64_t r0 = wb; r0 < we; r0 += S) {
+            int64_t row[U];
+            bool valid[U];
+            int4 xv[U][V];
+            float4 ax[U];
+            bool some = false;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                row[u] = r0 + u * R + g;
+                valid[u] = row[u] < we;
+                if constexpr (FILT) {   // (a sparse segment, or a leaf without a bitset in a filtered call)
+                    if (abits && valid[u]) {
+                        const int32_t doc = seg.ord_to_doc ? seg.ord_to_doc[row[u]] : (int32_t)row[u];
+                        valid[u] = (abits[doc >> 6] >> (doc & 63)) & 1ull;
+                    }
+                    some = some || valid[u];
+                }
+            }
+            // under a filter a step without an accepted row is skipped before its loads are issued (one test
+            // per step, ahead of all U groups' loads: those still overlap)
+            if constexpr (FILT)
+                if (!__ballot(some)) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                // loads on a clamped row, results masked (no load under a branch: those serialise)
+                const int64_t rc = row[u] < we ? row[u] : wb;
+                const int4* xr = X + rc * u8;
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const int f = t + j * L;
+                    const int4 x = load_i4_nt(xr + (f < u8 ? f : 0));
+                    const int m = (valid[u] && f < u8) ? -1 : 0;
+                    xv[u][j] = make_int4(x.x & m, x.y & m, x.z & m, x.w & m);
+                }
+                ax[u] = AX[rc];
+            }
+            const int rel0 = __builtin_amdgcn_readfirstlane((int)(r0 - wb));   // (wave-uniform) the step's first bit
+            if ((rel0 >> 6) != hm.idx) {
+                hm.flush(hw, qstride, p.wpw, p.q_count, lane);
+                mm.flush(mw, qstride, p.wpw, p.q_count, lane);
+                hm.idx = mm.idx = rel0 >> 6;
+            }
+            uint32_t cls = 0u;   // this lane's row groups: bit 2(u·NQ + b) sure, the next maybe
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float xnd = (sim == SIM_COSINE && valid[u]) ? seg.xnorm_f[row[u]] : 0.0f;
+                nvis += __popcll(__ballot(t == 0 && valid[u]));
+                cls |= classify(xv[u], ax[u], xnd, valid[u]) << (2 * NQ * u);
+            }
+            // lane j < R takes row group j's classes (every lane of a group holds the same); the step's rows
+            // r0 + u·R + j are bits (rel0 & 63) + u·R + j of the word
+            const uint32_t c = (uint32_t)__shfl((int)cls, (lane & (R - 1)) * L);
+#pragma unroll
+            for (int b = 0; b < NQ; ++b) {
+                uint64_t sb = 0ull, mb = 0ull;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int k = 2 * (u * NQ + b);
+                    sb |= __ballot(lane < R && ((c >> k) & 1u)) << (u * R);
+                    mb |= __ballot(lane < R && ((c >> (k + 1)) & 1u)) << (u * R);
+                }
+                hm.bits[b] |= sb << (rel0 & 63);
+                mm.bits[b] |= mb << (rel0 & 63);
+            }
+        }
+    }
+    hm.flush(hw, qstride, p.wpw, p.q_count, lane);
+    mm.flush(mw, qstride, p.wpw, p.q_count, lane);
+
+    if (lane == 0) {
+#pragma unroll
+        for (int b = 0; b < NQ; ++b)
+            if (b < p.q_count) p.counts[(size_t)b * p.n_tiles * 4 + wi] = (int32_t)hm.cnt[b];
+    }
+    if (p.visited && p.q0 == 0) add_visited_wg(&p.visited[tile.seg], nvis);
+}
+
+// ------------------------------------------------------------------------------------------------
+// settle: one workgroup per (tile, query of the pass).  A wave whose maybe words are all zero has nothing
+// to do; otherwise it walks them (walk_rows' compaction visits exactly the set bits), re-scores each row
+// with the fp32 scan's arithmetic, ORs the rows with score ≥ min_score into its own hit-mask words and adds
+// them to its count.  The rows it re-scored go to the view's device counter.
+// ------------------------------------------------------------------------------------------------
+template <int L, int V, bool L2K>
+__global__ __launch_bounds__(kBlock) void thr_settle_f32(ThrParams p) {
+    constexpr int R = 64 / L;
+    constexpr int UP = L * V;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t = lane & (L - 1), g = lane / L;
+    const int b = blockIdx.y;
+    const size_t wi = ((size_t)b * p.n_tiles + blockIdx.x) * 4 + wave;
+    const uint64_t* my = p.maybe + wi * p.wpw;
+    bool any = false;
+    for (int i0 = 0; i0 < p.wpw; i0 += 64)
+        if (i0 + lane < p.wpw) any = any || my[i0 + lane] != 0ull;
+    uint32_t nset = 0;
+    if (__ballot(any)) {   // (wave-uniform)
+        const TileDev tile = p.tiles[blockIdx.x];
+        const SegDev seg = p.segs[tile.seg];
+        const float4* __restrict__ X = static_cast<const float4*>(seg.rows);
+        const float4* __restrict__ Q = static_cast<const float4*>(p.q) + (size_t)b * UP;
+        const int units = p.units, sim = p.sim;
+        float4 qf[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) qf[j] = Q[t + j * L];
+        auto qat = [&](int j) -> float4 { return qf[j]; };
+        float qn = 0.0f;
+        if (!L2K && sim == SIM_COSINE) qn = thr_qnorm_f32<L, V>(qat);
+        const float ms = p.min_score[b];
+        int64_t wb, we;
+        thr_wave_range<R>(tile, wave, wb, we);
+        uint64_t* hw = p.mask + wi * p.wpw;
+        uint64_t bits = 0ull;   // the hit word in progress (wave-uniform)
+        int idx = 0;
+        uint32_t cnt = 0;
+        auto flush = [&]() {
+            if (bits != 0ull && idx < p.wpw) {
+                if (lane == 0) hw[idx] |= bits;   // this wave's own word: the scan's sure bits stay
+                cnt += (uint32_t)__popcll(bits);
+            }
+            bits = 0ull;
+        };
+        walk_rows<R>(0, we - wb, my, nullptr, lane, g, [&](const int64_t rel, bool valid, bool) {
+            const int64_t row = wb + rel;
+            float4 xv[V];
+            thr_load_row_f32<L, V, false>(X + row * units, valid, units, t, xv);
+            float xn = 0.0f;
+            if (!L2K && sim == SIM_COSINE && valid) xn = seg.xnorm_f[row];
+            const float sc = thr_score_f32<L, V, L2K>(xv, qat, sim, qn, xn);
+            nset += __popcll(__ballot(t == 0 && valid));
+            const int widx = __builtin_amdgcn_readfirstlane((int)rel) >> 6;   // lane 0: the step's first row
+            if (widx != idx) {
+                flush();
+                idx = widx;
+            }
+            const bool hit = valid && sc >= ms;
+            bits |= thr_step_bits<L>(hit, false, (int)rel, lane, t);
+        });
+        flush();
+        if (lane == 0 && cnt) p.counts[wi] += (int32_t)cnt;
+    }
+    add_visited_wg(p.settled, nset);
+}
+
+// ------------------------------------------------------------------------------------------------
 // offsets: one workgroup per (shard, query of the pass)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void thr_offsets(ThrParams p) {
@@ -423,6 +703,20 @@ const ThrFn kThrEmitI8[9] = {thr_emit_i8<4, 2>,  thr_emit_i8<8, 2>,  thr_emit_i8
                              thr_emit_i8<16, 4>, thr_emit_i8<16, 8>, thr_emit_i8<16, 12>,
                              thr_emit_i8<32, 8>, thr_emit_i8<64, 8>, thr_emit_i8<64, 16>};
 
+// the int8 first pass: the prefilter's lane configs by 16-byte units (sel_bounds_cfg's) × NQ × filter
+#define OSK_THR_SQ8(L, V)                                                                 \
+    {{thr_scan_sq8<L, V, 1, false>, thr_scan_sq8<L, V, 1, true>},                         \
+     {thr_scan_sq8<L, V, kThrNQ, false>, thr_scan_sq8<L, V, kThrNQ, true>}}
+#define OSK_THR_SETTLE(L, V) {thr_settle_f32<L, V, true>, thr_settle_f32<L, V, false>}
+const ThrFn kThrScanSq8[8][2][2] = {OSK_THR_SQ8(4, 1),  OSK_THR_SQ8(8, 1),  OSK_THR_SQ8(16, 1), OSK_THR_SQ8(16, 2),
+                                    OSK_THR_SQ8(16, 3), OSK_THR_SQ8(16, 4), OSK_THR_SQ8(32, 4), OSK_THR_SQ8(64, 4)};
+const ThrFn kThrSettleF32[9][2] = {OSK_THR_SETTLE(4, 2),  OSK_THR_SETTLE(8, 2),  OSK_THR_SETTLE(8, 4),
+                                   OSK_THR_SETTLE(16, 4), OSK_THR_SETTLE(16, 8), OSK_THR_SETTLE(16, 12),
+                                   OSK_THR_SETTLE(32, 8), OSK_THR_SETTLE(64, 8), OSK_THR_SETTLE(64, 16)};
+int thr_sq8_cfg(int u8) {
+    return u8 <= 4 ? 0 : u8 <= 8 ? 1 : u8 <= 16 ? 2 : u8 <= 32 ? 3 : u8 <= 48 ? 4 : u8 <= 64 ? 5 : u8 <= 128 ? 6 : 7;
+}
+
 // what every launch of a pass must satisfy; anything else is refused, never guessed
 bool thr_params_ok(int enc, int cfg, const ThrParams& p) {
     return (enc == ENC_FLOAT32 || enc == ENC_BYTE) && cfg >= 0 && cfg < 9 && p.sim >= 0 && p.sim <= 3 &&
@@ -459,6 +753,31 @@ hipError_t launch_thr_scan(int enc, int cfg, const ThrParams& p, hipStream_t s, 
         hipExtLaunchKernelGGL(fn, dim3(p.n_tiles), dim3(kBlock), lds, s, ev_start, ev_stop, 0, p);
     else
         hipLaunchKernelGGL(fn, dim3(p.n_tiles), dim3(kBlock), lds, s, p);
+    return hipGetLastError();
+}
+
+// the int8 pass's own arguments: the view's float32 config must be the one that splits the tiles
+static bool thr_sq8_params_ok(int cfg, const ThrParams& p) {
+    return thr_params_ok(ENC_FLOAT32, cfg, p) && p.n_tiles >= 1 && p.maybe && p.maybe != p.mask && p.rows8 &&
+           p.aux && p.q8 && p.qc && p.qnorm && p.qflags && p.settled && p.units8 >= 1 && p.units8 <= 256 &&
+           p.units8 == (p.dim + 15) / 16 && p.wave_R == 64 / kCfgLV[cfg][0];
+}
+
+hipError_t launch_thr_scan_sq8(int cfg, const ThrParams& p, hipStream_t s, hipEvent_t ev_start,
+                               hipEvent_t ev_stop) {
+    if (!thr_sq8_params_ok(cfg, p)) return hipErrorInvalidValue;
+    const ThrFn fn = kThrScanSq8[thr_sq8_cfg(p.units8)][p.q_count <= 1 ? 0 : 1][p.accept ? 1 : 0];
+    if (ev_start || ev_stop)
+        hipExtLaunchKernelGGL(fn, dim3(p.n_tiles), dim3(kBlock), 0, s, ev_start, ev_stop, 0, p);
+    else
+        hipLaunchKernelGGL(fn, dim3(p.n_tiles), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_thr_settle(int cfg, const ThrParams& p, hipStream_t s) {
+    if (!thr_sq8_params_ok(cfg, p)) return hipErrorInvalidValue;
+    const ThrFn fn = kThrSettleF32[cfg][p.sim == SIM_EUCLIDEAN ? 0 : 1];
+    hipLaunchKernelGGL(fn, dim3(p.n_tiles, p.q_count), dim3(kBlock), 0, s, p);
     return hipGetLastError();
 }
 
