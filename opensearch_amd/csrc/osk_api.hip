@@ -795,8 +795,8 @@ int32_t osk_view_create(osk_seg* const* segs, int32_t n_segs, const int32_t* seg
     OSK_HIP(v->d_tile_coff.reserve(sizeof(int32_t) * tile_coff.size()));
     OSK_HIP(v->d_tile_order.reserve(sizeof(int32_t) * tile_order.size()));
     OSK_HIP(v->d_seg_vrow.reserve(sizeof(int64_t) * n_segs));
-    OSK_HIP(v->d_counters.reserve(sizeof(unsigned long long) * 24));
-    OSK_HIP(hipMemsetAsync(v->d_counters.p, 0, sizeof(unsigned long long) * 24, st));
+    OSK_HIP(v->d_counters.reserve(sizeof(unsigned long long) * kCtrCount));
+    OSK_HIP(hipMemsetAsync(v->d_counters.p, 0, sizeof(unsigned long long) * kCtrCount, st));
     OSK_HIP(hipMemcpyAsync(v->d_seg_vrow.p, vrow.data(), sizeof(int64_t) * n_segs, hipMemcpyHostToDevice, st));
     OSK_HIP(hipMemcpyAsync(v->d_segs.p, sd.data(), sizeof(SegDev) * n_segs, hipMemcpyHostToDevice, st));
     if (!tiles.empty())
@@ -905,10 +905,19 @@ int32_t profile_end(osk_view* v, hipStream_t st, bool record) {
     return OSK_OK;
 }
 
-// (start, stop) events for launch q0 of a call that launches [0, nq) in chunks of kMaxNQ
+// (start, stop) events for launch q0 of a call that launches [0, nq) in chunks of `chunk` queries
 inline hipEvent_t launch_ev_start(const osk_view* v, int q0) { return v->profile && q0 == 0 ? v->ev0 : nullptr; }
-inline hipEvent_t launch_ev_stop(const osk_view* v, int q0, int nq) {
-    return v->profile && q0 + kMaxNQ >= nq ? v->ev1 : nullptr;
+inline hipEvent_t launch_ev_stop(const osk_view* v, int q0, int nq, int chunk = kMaxNQ) {
+    return v->profile && q0 + chunk >= nq ? v->ev1 : nullptr;
+}
+
+// the device's CUs (cached; the persistent kernels' grids and the wide tile table are sized by them)
+int view_cus(osk_view* v) {
+    if (v->n_cus <= 0 &&
+        (hipDeviceGetAttribute(&v->n_cus, hipDeviceAttributeMultiprocessorCount, v->device) != hipSuccess ||
+         v->n_cus <= 0))
+        v->n_cus = 256;
+    return v->n_cus;
 }
 
 // Nothing staged: every shard returns zero hits.
@@ -1347,10 +1356,7 @@ int32_t ensure_sq8w(osk_view* v, hipStream_t st) {
         // written for all 256 queries, so quarters of the scan tiles (≈ 244 rows at C2) would make the list
         // traffic rival the corpus.  Quarters here hold ≈ R / (2·CUs) rows, 256 … 16,384 (C2 ≈ 2k, C4 16k;
         // two to a few dozen per persistent workgroup), tiles never span segments, cut at multiples of 16.
-        if (v->n_cus <= 0 &&
-            (hipDeviceGetAttribute(&v->n_cus, hipDeviceAttributeMultiprocessorCount, v->device) != hipSuccess ||
-             v->n_cus <= 0))
-            v->n_cus = 256;
+        const int cus = view_cus(v);
         double R = 0.0;
         for (const osk_seg* sg : v->segs) R += (double)sg->n_rows;
         // (≥ 512 dims: quarters of R / (8·CUs), so the first pass — one round of the persistent grid — covers
@@ -1364,7 +1370,7 @@ int32_t ensure_sq8w(osk_view* v, hipStream_t st) {
         const int64_t qmax = 16384;
         const int64_t qr = g_tuning.sq8_wide_quarter_rows > 0
                                ? std::max<int64_t>(16, (int64_t)g_tuning.sq8_wide_quarter_rows & ~15ll)
-                               : std::min<int64_t>(qmax, std::max<int64_t>(256, (int64_t)(R / ((double)qdiv * v->n_cus)) + 15 & ~15ll));
+                               : std::min<int64_t>(qmax, std::max<int64_t>(256, (int64_t)(R / ((double)qdiv * cus)) + 15 & ~15ll));
         const int64_t trows = 4 * qr;
         std::vector<TileDev> wt;
         v->wshard_tile_begin.assign(v->n_shards + 1, 0);
@@ -1673,322 +1679,411 @@ bool sq8_wide_pick(const osk_view* v, int nq, bool filtered) {
     return g_tuning.sq8_wide_force || sq8_wide_us(R, nq, u8) <= sq8_narrow_us(R, nq, u8, v->dim);
 }
 
-// Certified int8 prefilter search (float32, k ≤ kKQ): int8 scan → settle per slice of tiles (exact
+// The wide kernels' pilot rows per quarter (tune sq8_wide_pilot_rows; 0: 128, 256 at ≥ 512 dims, where the
+// pilot's steps are 32 rows and the better floors pay: C3 b256 3.76 → 3.71 ms, C4's 96 dims 22.98 → 23.27 ms,
+// profiles/r05p/tune50_*).
+// At least ≈ 64k pilot rows per shard: the floor is the k-th best of the shard's quarter maxima, so a
+// shard of few quarters (6.5M rows over 8 shards: 64 quarters of 12.7k rows) sampled at 128 rows a
+// quarter floored the first pass at ≈ its 1,000th best row, and the rows kernel's queues overflowed for
+// every query (exact re-scans of the overflowed quarters); up to 1,024 rows a quarter.
+int sq8_wide_pilot_rows(const osk_view* v) {
+    const int prows = g_tuning.sq8_wide_pilot_rows.load();
+    if (prows > 0) return prows;
+    const int pr = sq8_wide_ks(v->units8) >= 8 ? 256 : kWidePilotRowsDefault;
+    const int qps = std::max(1, 4 * v->n_wtiles / std::max(1, v->n_shards));   // quarters per shard
+    const int want = (kWidePilotSample + qps - 1) / qps;
+    return std::max(pr, std::min(1024, (want + 127) / 128 * 128));
+}
+// The wide kernels' two passes: the first 1/phase of the nql quarters (tile order: every shard) under the
+// pilot's floors, then the rest under floors raised by the first pass's list maxima.  Returns the first
+// pass's quarters (0: one pass).
+// (the first pass takes whole rounds of the persistent grid, at least one: a small view's 1/phase
+// would idle the chip, and a partial round leaves a tail)
+int sq8_wide_first_pass(int nql, int wgrid) {
+    const int phase = g_tuning.sq8_wide_phase;
+    const int rounds = std::max(1, (int)std::lround((double)nql / ((double)phase * wgrid)));
+    return phase > 1 ? std::min(nql / 2, rounds * wgrid) : 0;
+}
+
+// ---- Certified int8 prefilter search (float32, k ≤ kKQ): int8 scan → settle per slice of tiles (exact
 // re-score of the rows the certificate cannot exclude; a tile whose list overflowed is re-scanned
-// exactly inside the settle) → per-shard merge.  Nothing waits on the host.
-// ws_q / ws_qnorm hold the padded fp32 queries and |q|² (device order).
-int32_t sq8_search(osk_view* v, const void* d_queries, int nq, int k, int UP, const uint64_t* const* d_accept,
-                   uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st) {
-    int32_t rc = ensure_sq8(v, st);
-    if (rc) return rc;
-    const int u8 = v->units8, S = v->n_shards;
-    const int nq_pad = (nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;
-    // batches of ≥ sq8_mfma_min queries: the int8 MFMA scan, 16 queries per launch; else the VALU
-    // scan, ≤ 8 per launch.  Filtered VALU scans run over the compacted accepted ordinals.  A single
-    // unfiltered query scans the 6-bit tier where the view has one.
-    const bool use_mfma = g_tuning.sq8_mfma_min > 0 && nq >= g_tuning.sq8_mfma_min && sq8_mfma_supported(u8);
-    // large unfiltered batches of ≤ 768-dim rows: one corpus pass per kWideQ queries (osk_sq8w.hip)
-    const bool use_wide = use_mfma && !g_tuning.sq8_force_fallback && sq8_wide_pick(v, nq, d_accept != nullptr);
-    // the 6-bit tier: single unfiltered queries, every segment's calibration probing or on.  The shared
-    // lock keeps a segment's copy alive from this check to the launches (fold_probe frees it under the
-    // exclusive one, with hipFreeAsync behind the events of the launches still reading it: no device wait)
-    rc = fold_probe(v, st);
-    if (rc) return rc;
-    std::shared_lock<std::shared_mutex> tier_lock(g_sq6_free_mu, std::defer_lock);
-    bool use6 = nq == 1 && !d_accept && !use_mfma && v->sq6_ready && g_tuning.sq6;
-    bool probing = false;
+// exactly inside the settle) → per-shard merge.  Nothing waits on the host.  sq8_search decides on one of
+// four scans (sq8_decide), prepares the queries, runs the scan (scan_valu, scan_mfma, scan_wide, scan_sq6:
+// each with its own copies, workspace and parameter block) and settles the lists the scan reports. ----
+enum class Sq8Strategy { kValu, kMfma, kWide, kSq6 };
+struct Sq8Plan {
+    Sq8Strategy strategy;
+    bool gather;    // kValu: a filtered scan over the compacted accepted ordinals
+    bool probing;   // kSq6: some segment is still calibrating the tier (it may yet turn it off)
+    bool probe6;    // kSq6: this call counts its int8 re-bounds per segment (one probe in flight per view)
+};
+// one search call's arguments
+struct Sq8Call {
+    osk_view* v;
+    int nq, k;
+    const uint64_t* const* d_accept;
+    uint64_t* d_shard_keys;
+    int32_t* d_shard_counts;
+    int64_t* d_visited;
+    hipStream_t st;
+};
+// What a scan reports to the settle: its wave lists (ws_sq8cand, ws_sq8lb, ws_lbmax), the rows per
+// wave-iteration that split a tile among its waves, and the tile and slice tables the lists are over.
+struct Sq8Lists {
+    int n_lists;
+    int scan_R;
+    const TileDev* tiles;                    // (exact re-scan of an overflowed list)
+    const int4* slices;
+    const int32_t* shard_slice_begin;
+    int n_slices;
+    GatherSplit gather;                      // gather scans: the scan's split
+    const int32_t* wide_shard_tile_begin;    // wide scans: one settle workgroup per (shard, query); else null
+};
+
+// Batches of ≥ sq8_mfma_min queries: the int8 MFMA scan, ≤ 32 queries per launch — large unfiltered batches
+// of ≤ 768-dim rows on the wide kernels when the cost model picked them (wide_pick: sq8_wide_pick), one
+// corpus pass per kWideQ queries (osk_sq8w.hip); else the VALU scan, ≤ 8 per launch, filtered ones over the
+// compacted accepted ordinals.  A single unfiltered query scans the 6-bit tier where the view has one
+// (DESIGN.md §3f): every segment's calibration probing or on.  The shared lock is taken for that check and
+// keeps a segment's copy alive from it to the launches (fold_probe frees it under the exclusive one, with
+// hipFreeAsync behind the events of the launches still reading it: no device wait).
+Sq8Plan sq8_decide(const osk_view* v, int nq, bool filtered, bool wide_pick,
+                   std::shared_lock<std::shared_mutex>& tier_lock) {
+    Sq8Plan plan{Sq8Strategy::kValu, false, false, false};
+    if (g_tuning.sq8_mfma_min > 0 && nq >= g_tuning.sq8_mfma_min && sq8_mfma_supported(v->units8)) {
+        plan.strategy = !g_tuning.sq8_force_fallback && wide_pick ? Sq8Strategy::kWide : Sq8Strategy::kMfma;
+        return plan;
+    }
+    bool use6 = nq == 1 && !filtered && v->sq6_ready && g_tuning.sq6;
     if (use6) {
         tier_lock.lock();
         for (const osk_seg* sg : v->segs) {
             const int st6 = sg->sq6_state.load(std::memory_order_acquire);
             use6 = use6 && st6 != 2 && sg->d_q6;
-            probing |= st6 == 0;
+            plan.probing |= st6 == 0;
         }
     }
-    // calibration: this call counts its int8 re-bounds per segment (one probe in flight per view)
-    const bool probe6 = use6 && probing && !v->probe_pending;
-    const int ns = (int)v->segs.size();
+    if (use6) {
+        plan.strategy = Sq8Strategy::kSq6;
+        plan.probe6 = plan.probing && !v->probe_pending;
+    } else {
+        plan.probing = false;
+        plan.gather = filtered && g_tuning.filter_gather;
+    }
+    return plan;
+}
+
+// The 6-bit tier's share of the prologue: a probe call's per-segment re-bound counts (zeroed), and the
+// tier's query form and floor buckets for the fused prep to fill.
+int32_t sq6_prep(osk_view* v, int nq_pad, bool probe6, hipStream_t st, Sq6Prep& q6) {
+    const size_t ns = v->segs.size();
     if (probe6) {
         OSK_HIP(v->d_seg_rebound.reserve(sizeof(unsigned long long) * ns));
         OSK_HIP(v->h_seg_rebound.reserve(sizeof(unsigned long long) * ns));
         if (!v->ev_probe) OSK_HIP(hipEventCreateWithFlags(&v->ev_probe, hipEventDisableTiming));
         OSK_HIP(hipMemsetAsync(v->d_seg_rebound.p, 0, sizeof(unsigned long long) * ns, st));
     }
+    q6.C = sq6_chunks(v->dim);
+    q6.floor_n = v->n_shards * (kFloorBuckets + 1) * kFloorStride;   // buckets + the floor cell per shard
+    OSK_HIP(v->ws_q6.reserve((size_t)nq_pad * 256 * q6.C));
+    OSK_HIP(v->ws_qc6.reserve(sizeof(float4) * nq_pad));
+    OSK_HIP(v->ws_floor.reserve(sizeof(uint32_t) * (size_t)nq_pad * q6.floor_n));
+    q6.q6 = v->ws_q6.as<uint32_t>();
+    q6.qc6 = v->ws_qc6.as<float4>();
+    q6.floor = v->ws_floor.as<uint32_t>();
+    return OSK_OK;
+}
+
+// One launch: padded fp32 queries (ws_q), |q|² (device order, ws_qnorm), int8 queries + bound terms (and the
+// 6-bit tier's query form, floor buckets zeroed), flags = 0.
+int32_t sq8_prep_queries(const Sq8Call& c, const void* d_queries, int UP, const Sq8Plan& plan) {
+    osk_view* v = c.v;
+    const int u8 = v->units8, nq_pad = (c.nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;
+    Sq6Prep q6{};
+    if (plan.strategy == Sq8Strategy::kSq6) {
+        const int32_t rc = sq6_prep(v, nq_pad, plan.probe6, c.st, q6);
+        if (rc) return rc;
+    }
     OSK_HIP(v->ws_q8.reserve((size_t)nq_pad * u8 * 16));
     OSK_HIP(v->ws_qc.reserve(sizeof(float4) * nq_pad));
-    OSK_HIP(v->ws_flags.reserve(sizeof(int) * nq));
-    Sq6Prep q6{};
-    if (use6) {
-        q6.C = sq6_chunks(v->dim);
-        q6.floor_n = S * (kFloorBuckets + 1) * kFloorStride;   // buckets + the floor cell per shard
-        OSK_HIP(v->ws_q6.reserve((size_t)nq_pad * 256 * q6.C));
-        OSK_HIP(v->ws_qc6.reserve(sizeof(float4) * nq_pad));
-        OSK_HIP(v->ws_floor.reserve(sizeof(uint32_t) * (size_t)nq_pad * q6.floor_n));
-        q6.q6 = v->ws_q6.as<uint32_t>();
-        q6.qc6 = v->ws_qc6.as<float4>();
-        q6.floor = v->ws_floor.as<uint32_t>();
-    }
-    // one launch: padded fp32 queries, |q|² (device order), int8 queries + bound terms (and the 6-bit
-    // tier's query form, floor buckets zeroed), flags = 0
-    OSK_HIP(launch_sq8_prep(v->cfg, static_cast<const float*>(d_queries), v->dim, nq, nq_pad, UP, u8,
+    OSK_HIP(v->ws_flags.reserve(sizeof(int) * c.nq));
+    OSK_HIP(launch_sq8_prep(v->cfg, static_cast<const float*>(d_queries), v->dim, c.nq, nq_pad, UP, u8,
                             v->ws_q.as<float4>(), v->ws_qnorm.as<float>(), v->ws_q8.p, v->ws_qc.as<float4>(),
-                            v->ws_flags.as<int>(), st, q6));
-    const bool gather = d_accept && !use_mfma && g_tuning.filter_gather;
-    if (gather) {
-        rc = ensure_gather(v, st);
-        if (rc) return rc;
-    }
-    int n_scan_tiles = gather ? v->n_gtiles : v->n_tiles;
-    if (use_wide) {   // its own copy and tile table (ensure_sq8w)
-        rc = ensure_sq8w(v, st);
-        if (rc) return rc;
-        n_scan_tiles = v->n_wtiles;
-    }
-    const size_t nl = (size_t)nq * 4 * n_scan_tiles * kKQ;
+                            v->ws_flags.as<int>(), c.st, q6));
+    return OSK_OK;
+}
+
+// The wave lists of a scan over n_tiles tiles (4 per tile and query), the fields every strategy's kernels
+// share, and the report of a scan over the view's own tiles.
+int32_t sq8_lists(const Sq8Call& c, int n_tiles, int scan_R, Sq8Common& p, Sq8Lists& out) {
+    osk_view* v = c.v;
+    const size_t nl = (size_t)c.nq * 4 * n_tiles * kKQ;
     OSK_HIP(v->ws_sq8cand.reserve(sizeof(uint64_t) * nl));
     OSK_HIP(v->ws_sq8lb.reserve(sizeof(uint32_t) * nl));
-    OSK_HIP(v->ws_lbmax.reserve(sizeof(uint32_t) * (size_t)nq * 4 * n_scan_tiles));
-    Sq8Params p{};
+    OSK_HIP(v->ws_lbmax.reserve(sizeof(uint32_t) * (size_t)c.nq * 4 * n_tiles));
     p.segs = v->d_segs.as<SegDev>();
     p.tiles = v->d_tiles.as<TileDev>();
-    p.accept = d_accept;
+    p.accept = c.d_accept;
     p.rows8 = v->d_sq8_rows.as<const int4*>();
     p.aux = v->d_sq8_aux.as<const float4*>();
     p.seg_vrow = v->d_seg_vrow.as<int64_t>();
     p.cand = v->ws_sq8cand.as<uint64_t>();
     p.cand_lb = v->ws_sq8lb.as<uint32_t>();
     p.list_lbmax = v->ws_lbmax.as<uint32_t>();
-    p.visited = reinterpret_cast<unsigned long long*>(d_visited);
-    p.n_tiles = n_scan_tiles;
-    p.n_lists = 4 * n_scan_tiles;
+    p.visited = reinterpret_cast<unsigned long long*>(c.d_visited);
+    p.n_tiles = n_tiles;
+    p.n_lists = 4 * n_tiles;
     v->sq8_lists_last = p.n_lists;
-    p.units8 = u8;
+    p.units8 = v->units8;
     p.sim = v->sim;
     p.gam = v->sq8_gam;
     p.g2 = v->sq8_g2;
     p.cos_slack = v->sq8_cos_slack;
-    if (gather) {   // accepted ordinals of every segment, compacted (count, then prefix + write)
+    p.k = c.k;
+    p.n_shards = v->n_shards;
+    p.counters = v->d_counters.as<unsigned long long>();
+    p.ablate = g_tuning.sq8_mfma_ablate;
+    out = Sq8Lists{p.n_lists, scan_R, p.tiles, v->d_slices.as<int4>(), v->d_shard_slice_begin.as<int32_t>(),
+                   v->n_slices, GatherSplit{}, nullptr};
+    return OSK_OK;
+}
+// ...and the launch's queries [q0, q0 + chunk) of nq
+void sq8_chunk(const osk_view* v, Sq8Common& p, int q0, int chunk, int nq) {
+    p.q0 = q0;
+    p.q_count = std::min(chunk, nq - q0);
+    p.q8 = v->ws_q8.as<int4>() + (size_t)q0 * v->units8;
+    p.qc = v->ws_qc.as<float4>() + q0;
+    p.qn_dev = v->ws_qnorm.as<float>() + q0;
+}
+
+// The VALU scan, ≤ kMaxNQ queries per launch; gather: over the accepted ordinals of every segment,
+// compacted first (count, then prefix + write).
+int32_t scan_valu(const Sq8Call& c, bool gather, Sq8Lists& out) {
+    osk_view* v = c.v;
+    int32_t rc = gather ? ensure_gather(v, c.st) : OSK_OK;
+    if (rc) return rc;
+    Sq8ScanParams p{};
+    rc = sq8_lists(c, gather ? v->n_gtiles : v->n_tiles, 64 / sq8_lanes(v->units8), p, out);
+    if (rc) return rc;
+    if (gather) {
         FilterParams fp{};
-        fp.segs = v->d_segs.as<SegDev>();
-        fp.tiles = v->d_tiles.as<TileDev>();
-        fp.accept = d_accept;
-        fp.seg_vrow = v->d_seg_vrow.as<int64_t>();
+        fp.segs = p.segs;
+        fp.tiles = p.tiles;
+        fp.accept = c.d_accept;
+        fp.seg_vrow = p.seg_vrow;
         fp.seg_tiles = v->d_seg_tiles.as<int2>();
         fp.tcnt = v->ws_tcnt.as<int32_t>();
         fp.scnt = v->ws_scnt.as<int32_t>();
         fp.comp = v->ws_comp.as<uint32_t>();
         fp.n_tiles = v->n_tiles;
         fp.n_segs = (int)v->segs.size();
-        OSK_HIP(launch_filter_compact(fp, st));
-        p.gtiles = v->d_gtiles.as<int4>();
-        p.comp = fp.comp;
-        p.scnt = fp.scnt;
-        p.gather_min = g_tuning.gather_min;
+        OSK_HIP(launch_filter_compact(fp, c.st));
+        p.gather = GatherSplit{v->d_gtiles.as<int4>(), fp.comp, fp.scnt, g_tuning.gather_min};
+        out.gather = p.gather;
+        out.slices = v->d_gslices.as<int4>();
+        out.shard_slice_begin = v->d_gshard_slice_begin.as<int32_t>();
+        out.n_slices = v->n_gslices;
     }
-    const int chunk = use_wide ? kWideQ : use_mfma ? (int)g_tuning.sq8_mfma_queries : kMaxNQ;
-    if (use_mfma) {
-        rc = ensure_sq8t(v, st);
-        if (rc) return rc;
-        p.rows8t = v->d_sq8_rows_t.as<const int4*>();
-        p.auxt = v->d_sq8_auxt.as<const float4*>();
-        const size_t qmax = use_wide ? kWideQ : kMfmaQueries;
-        // pilot keys: per (query, list) of the table the launch walks — the wide kernel's own quarters
-        // (4 per wide tile, qi·4·n_wtiles + list) or the scan tiles' (64 sampled keys per tile); the two
-        // tables differ in size (tiles_target, views past ≈ 400M rows), so size by the one in use
-        const size_t pilot_keys = use_wide ? qmax * 4 * (size_t)std::max(1, v->n_wtiles)
-                                           : qmax * 64 * (size_t)std::max(1, v->n_tiles);
-        OSK_HIP(v->ws_pilot.reserve(sizeof(uint64_t) * pilot_keys));
-        OSK_HIP(v->ws_thr.reserve(sizeof(uint64_t) * qmax * S * 64));
-        OSK_HIP(v->ws_thr_counts.reserve(sizeof(int32_t) * qmax * S));
-        if (use_wide) OSK_HIP(v->ws_wfloor.reserve(sizeof(uint32_t) * 2 * kWideQ * S));
+    for (int q0 = 0; q0 < c.nq; q0 += kMaxNQ) {
+        sq8_chunk(v, p, q0, kMaxNQ, c.nq);
+        OSK_HIP(launch_sq8_scan(p.q_count, p, c.st, launch_ev_start(v, q0), launch_ev_stop(v, q0, c.nq)));
     }
-    for (int q0 = 0; q0 < nq; q0 += chunk) {
-        p.q0 = q0;
-        p.q_count = std::min(chunk, nq - q0);
-        p.q8 = v->ws_q8.as<int4>() + (size_t)q0 * u8;
-        p.qc = v->ws_qc.as<float4>() + q0;
-        p.qn_dev = v->ws_qnorm.as<float>() + q0;
-        hipEvent_t e0 = v->profile && q0 == 0 ? v->ev0 : nullptr;
-        hipEvent_t e1 = v->profile && q0 + chunk >= nq ? v->ev1 : nullptr;
-        if (use_wide) {
-            // pilot: the first step of every quarter → per (query, quarter) the best lower-bound key (and the
-            // quarter's list maximum zeroed) → per (query, shard) the k-th best of them floors the main pass
-            if (v->n_cus <= 0 &&
-                (hipDeviceGetAttribute(&v->n_cus, hipDeviceAttributeMultiprocessorCount, v->device) != hipSuccess ||
-                 v->n_cus <= 0))
-                v->n_cus = 256;
-            // persistent workgroups: one per CU (sq8_wide_grid overrides it: the tests' LDS-cap grid doubling)
-            const int wgrid = g_tuning.sq8_wide_grid > 0 ? (int)g_tuning.sq8_wide_grid : v->n_cus;
-            p.wide_grid = wgrid;
-            p.rows8t = v->d_sq8_rows_w.as<const int4*>();   // (the wide copy: one scale per 16-row group)
-            p.tiles = v->d_wtiles.as<TileDev>();
-            p.tile_order = v->d_wtile_order.as<int32_t>();
-            p.k = k;
-            p.n_shards = S;
-            p.ablate = g_tuning.sq8_mfma_ablate;
-            p.counters = v->d_counters.as<unsigned long long>();   // (testing build: event counts)
-            p.pilot = 1;
-            // (0: 128 rows per quarter, 256 at ≥ 512 dims, where the pilot's steps are 32 rows and the better
-            // floors pay: C3 b256 3.76 → 3.71 ms, C4's 96 dims 22.98 → 23.27 ms, profiles/r05p/tune50_*)
-            // At least ≈ 64k pilot rows per shard: the floor is the k-th best of the shard's quarter maxima, so a
-            // shard of few quarters (6.5M rows over 8 shards: 64 quarters of 12.7k rows) sampled at 128 rows a
-            // quarter floored the first pass at ≈ its 1,000th best row, and the rows kernel's queues overflowed for
-            // every query (exact re-scans of the overflowed quarters); up to 1,024 rows a quarter.
-            const int prows = g_tuning.sq8_wide_pilot_rows.load();
-            int pr = prows > 0 ? prows : (sq8_wide_ks(u8) >= 8 ? 256 : kWidePilotRowsDefault);
-            if (prows <= 0) {
-                const int qps = std::max(1, 4 * v->n_wtiles / std::max(1, S));   // quarters per shard
-                const int want = (kWidePilotSample + qps - 1) / qps;
-                pr = std::max(pr, std::min(1024, (want + 127) / 128 * 128));
-            }
-            p.pilot_rows = pr;
-            p.wide_defer = g_tuning.sq8_wide_defer;
-            p.pilot_keys = v->ws_pilot.as<uint64_t>();
-            p.quarter_begin = 0;
-            p.quarter_end = 0;
-            p.floors = nullptr;
-            p.quarter_bm = v->d_quarter_bm.as<const float4>();
-            p.wide_qtable = v->d_wqtable.p;
-            p.wide_claim = g_tuning.sq8_wide_rows_claim;
-            // ≤ 128 dims: the pilot and the main passes without a step barrier (sq8_wide_rows, osk_sq8w.hip)
-            const bool rows = g_tuning.sq8_wide_rows && sq8_wide_rows_supported(u8);
-            p.wide_qcap = rows ? (int)g_tuning.sq8_wide_rows_qcap : 0;
-            if (rows)
-                OSK_HIP(launch_sq8_wide_rows(p, st, e0, nullptr));
-            else
-                OSK_HIP(launch_sq8_wide(p, st, e0, nullptr));
-            const int nql = 4 * v->n_wtiles;
-            const int32_t* sqb = v->d_shard_quarter_begin.as<int32_t>();
-            uint32_t* floor_a = v->ws_wfloor.as<uint32_t>();
-            uint32_t* floor_b = floor_a + (size_t)kWideQ * S;
-            OSK_HIP(launch_wide_floor(nullptr, v->ws_pilot.as<uint64_t>(), nql, sqb, S, p.q_count, k, nullptr, floor_a,
-                                      st));
-            p.pilot = 0;
-            p.floors = floor_a;
-            // two passes: the first 1/phase of the quarters (tile order: every shard) under the pilot's floors,
-            // then the rest under floors raised by the first pass's list maxima (the lists of the second pass
-            // read as empty until it writes them)
-            const int phase = g_tuning.sq8_wide_phase;
-            // (the first pass takes whole rounds of the persistent grid, at least one: a small view's 1/phase
-            // would idle the chip, and a partial round leaves a tail)
-            const int rounds = std::max(1, (int)std::lround((double)nql / ((double)phase * wgrid)));
-            const int n_a = phase > 1 ? std::min(nql / 2, rounds * wgrid) : 0;
-            auto main_pass = [&](hipEvent_t ev) {
-                return rows ? launch_sq8_wide_rows(p, st, nullptr, ev) : launch_sq8_wide(p, st, nullptr, ev);
-            };
-            if (n_a > 0) {   // (the pilot zeroed every list maximum: the second pass's read as empty)
-                uint32_t* lbm = p.list_lbmax + (size_t)q0 * nql;
-                p.quarter_end = n_a;
-                OSK_HIP(main_pass(nullptr));
-                OSK_HIP(launch_wide_floor(lbm, nullptr, nql, sqb, S, p.q_count, k, floor_a, floor_b, st));
-                p.quarter_begin = n_a;
-                p.quarter_end = 0;
-                p.floors = floor_b;
-            }
-            OSK_HIP(main_pass(e1));
-        } else if (use_mfma) {
-            // pilot: 16 sampled rows per wave → per (query, tile) the top k sampled lower bounds →
-            // per (query, shard) the top k; its k-th floors the main pass's quick thresholds
-            // (sq8_mfma comment)
-            p.k = k;
-            p.n_shards = S;
-            p.nt = g_tuning.sq8_mfma_nt;
-            p.ring_slots = sq8_ring_slots(u8, p.q_count > 16 ? 2 : 1, g_tuning.sq8_mfma_ring);
-            p.ablate = g_tuning.sq8_mfma_ablate;
-            p.pilot = 1;
-            p.pilot_keys = v->ws_pilot.as<uint64_t>();
-            OSK_HIP(launch_sq8_mfma(p, st, e0, nullptr));
-            OSK_HIP(launch_merge_shards(v->ws_pilot.as<uint64_t>(), v->n_tiles, v->d_shard_tile_begin.as<int32_t>(),
-                                        S, p.q_count, k, v->ws_thr.as<uint64_t>(), v->ws_thr_counts.as<int32_t>(), st));
-            p.pilot = 0;
-            p.thr_keys = v->ws_thr.as<uint64_t>();
-            p.thr_counts = v->ws_thr_counts.as<int32_t>();
-            OSK_HIP(launch_sq8_mfma(p, st, nullptr, e1));
-        } else if (use6) {
-            p.rows6 = v->d_sq6_rows.as<const void*>();
-            p.aux6 = v->d_sq6_aux.as<const float4*>();
-            p.q6 = v->ws_q6.as<int4>() + (size_t)q0 * 16 * q6.C;
-            p.qc6 = v->ws_qc6.as<float4>() + q0;
-            p.floor = q6.floor;
-            p.k = k;
-            p.n_shards = S;
-            p.counters = v->d_counters.as<unsigned long long>();
-            p.ablate = g_tuning.sq8_mfma_ablate;
-            p.tile_order = v->d_tile_order.as<int32_t>();
-            if (v->n_cus <= 0 &&
-                (hipDeviceGetAttribute(&v->n_cus, hipDeviceAttributeMultiprocessorCount, v->device) != hipSuccess ||
-                 v->n_cus <= 0))
-                v->n_cus = 256;
-            p.wide_grid = v->n_cus;   // (the persistent re-bound's grid: 4 workgroups per CU)
-            p.n_segs = ns;
-            p.rb_stride = g_tuning.sq6_rebound_stride;
-            p.rb_retest = g_tuning.sq6_rebound_retest;
-            p.rb_wg_per_cu = g_tuning.sq6_rebound_wgs;
-            OSK_HIP(v->ws_cand6.reserve(sizeof(uint2) * (size_t)p.n_lists * kSq6Cap));
-            OSK_HIP(v->ws_cnt6.reserve(sizeof(int32_t) * (size_t)nq * p.n_lists));
-            p.cand6 = v->ws_cand6.as<uint2>();
-            p.cnt6 = v->ws_cnt6.as<int32_t>();
-            p.cap6 = kSq6Cap;
-            p.seg_rebound = probe6 ? v->d_seg_rebound.as<unsigned long long>() : nullptr;
-            OSK_HIP(launch_sq6_scan(p, v->dim, st, e0, e1));
-            if (probing) {   // a segment may still turn the tier off: its free waits for this launch
-                rc = sq6_track_launch(v, st);
-                if (rc) return rc;
-            }
-        } else {
-            OSK_HIP(launch_sq8_scan(p.q_count, p, st, e0, e1));
-        }
+    return OSK_OK;
+}
+
+// sq8_mfma, sq8_mfma_queries (16 or 32) per launch.  Pilot: 16 sampled rows per wave → per (query, tile) the
+// top k sampled lower bounds → per (query, shard) the top k; its k-th floors the main pass's quick
+// thresholds (sq8_mfma comment).
+int32_t scan_mfma(const Sq8Call& c, Sq8Lists& out) {
+    osk_view* v = c.v;
+    const int S = v->n_shards;
+    Sq8MfmaParams p{};
+    int32_t rc = sq8_lists(c, v->n_tiles, kMfmaScanR, p, out);
+    if (rc || (rc = ensure_sq8t(v, c.st)) != OSK_OK) return rc;
+    // pilot keys: per (query, tile) 64 sampled keys
+    OSK_HIP(v->ws_pilot.reserve(sizeof(uint64_t) * kMfmaQueries * 64 * (size_t)std::max(1, v->n_tiles)));
+    OSK_HIP(v->ws_thr.reserve(sizeof(uint64_t) * kMfmaQueries * S * 64));
+    OSK_HIP(v->ws_thr_counts.reserve(sizeof(int32_t) * kMfmaQueries * S));
+    p.rows8t = v->d_sq8_rows_t.as<const int4*>();
+    p.nt = g_tuning.sq8_mfma_nt;
+    p.pilot_keys = v->ws_pilot.as<uint64_t>();
+    p.thr_keys = v->ws_thr.as<uint64_t>();
+    p.thr_counts = v->ws_thr_counts.as<int32_t>();
+    const int chunk = g_tuning.sq8_mfma_queries;
+    for (int q0 = 0; q0 < c.nq; q0 += chunk) {
+        sq8_chunk(v, p, q0, chunk, c.nq);
+        p.ring_slots = sq8_ring_slots(p.units8, p.q_count > 16 ? 2 : 1, g_tuning.sq8_mfma_ring);
+        p.pilot = 1;
+        OSK_HIP(launch_sq8_mfma(p, c.st, launch_ev_start(v, q0), nullptr));
+        OSK_HIP(launch_merge_shards(p.pilot_keys, v->n_tiles, v->d_shard_tile_begin.as<int32_t>(), S, p.q_count, c.k,
+                                    v->ws_thr.as<uint64_t>(), v->ws_thr_counts.as<int32_t>(), c.st));
+        p.pilot = 0;
+        OSK_HIP(launch_sq8_mfma(p, c.st, nullptr, launch_ev_stop(v, q0, c.nq, chunk)));
     }
-    rc = profile_end(v, st, false);
+    return OSK_OK;
+}
+
+// The wide kernels, kWideQ queries per launch, over their own copy and tile table (ensure_sq8w).  Pilot: the
+// first rows of every quarter → per (query, quarter) the best lower-bound key (and the quarter's list
+// maximum zeroed) → per (query, shard) the k-th best of them floors the main passes (sq8_wide_first_pass).
+int32_t scan_wide(const Sq8Call& c, Sq8Lists& out) {
+    osk_view* v = c.v;
+    const int S = v->n_shards;
+    int32_t rc = ensure_sq8w(v, c.st);
     if (rc) return rc;
-    const int n_slices = gather ? v->n_gslices : v->n_slices;
-    OSK_HIP(v->ws_part.reserve(sizeof(uint64_t) * (size_t)nq * n_slices * k));
+    Sq8WideParams p{};
+    rc = sq8_lists(c, v->n_wtiles, kMfmaScanR, p, out);
+    if (rc) return rc;
+    out.tiles = v->d_wtiles.as<TileDev>();
+    out.wide_shard_tile_begin = v->d_wshard_tile_begin.as<int32_t>();
+    // pilot keys: per (query, quarter) of the kernels' own table (4 per wide tile, qi·4·n_wtiles + list)
+    OSK_HIP(v->ws_pilot.reserve(sizeof(uint64_t) * kWideQ * 4 * (size_t)std::max(1, v->n_wtiles)));
+    OSK_HIP(v->ws_wfloor.reserve(sizeof(uint32_t) * 2 * kWideQ * S));
+    // persistent workgroups: one per CU (sq8_wide_grid overrides it: the tests' LDS-cap grid doubling)
+    p.wide_grid = g_tuning.sq8_wide_grid > 0 ? (int)g_tuning.sq8_wide_grid : view_cus(v);
+    p.rows8w = v->d_sq8_rows_w.as<const int4*>();
+    p.auxt = v->d_sq8_auxt.as<const float4*>();
+    p.wtiles = v->d_wtiles.as<TileDev>();
+    p.tile_order = v->d_wtile_order.as<int32_t>();
+    p.pilot_rows = sq8_wide_pilot_rows(v);
+    p.wide_defer = g_tuning.sq8_wide_defer;
+    p.pilot_keys = v->ws_pilot.as<uint64_t>();
+    p.quarter_bm = v->d_quarter_bm.as<const float4>();
+    p.wide_qtable = v->d_wqtable.p;
+    p.wide_claim = g_tuning.sq8_wide_rows_claim;
+    // ≤ 128 dims: the pilot and the main passes without a step barrier (sq8_wide_rows, osk_sq8w.hip)
+    const bool rows = g_tuning.sq8_wide_rows && sq8_wide_rows_supported(p.units8);
+    p.wide_qcap = rows ? (int)g_tuning.sq8_wide_rows_qcap : 0;
+    auto launch = [&](hipEvent_t e0, hipEvent_t e1) {
+        return rows ? launch_sq8_wide_rows(p, c.st, e0, e1) : launch_sq8_wide(p, c.st, e0, e1);
+    };
+    const int nql = p.n_lists;
+    const int n_a = sq8_wide_first_pass(nql, p.wide_grid);
+    const int32_t* sqb = v->d_shard_quarter_begin.as<int32_t>();
+    uint32_t* floor_a = v->ws_wfloor.as<uint32_t>();
+    uint32_t* floor_b = floor_a + (size_t)kWideQ * S;
+    for (int q0 = 0; q0 < c.nq; q0 += kWideQ) {
+        sq8_chunk(v, p, q0, kWideQ, c.nq);
+        p.pilot = 1;
+        p.quarter_begin = 0;
+        p.quarter_end = 0;
+        p.floors = nullptr;
+        OSK_HIP(launch(launch_ev_start(v, q0), nullptr));
+        OSK_HIP(launch_wide_floor(nullptr, p.pilot_keys, nql, sqb, S, p.q_count, c.k, nullptr, floor_a, c.st));
+        p.pilot = 0;
+        p.floors = floor_a;
+        if (n_a > 0) {   // (the pilot zeroed every list maximum: the second pass's read as empty until it writes them)
+            p.quarter_end = n_a;
+            OSK_HIP(launch(nullptr, nullptr));
+            OSK_HIP(launch_wide_floor(p.list_lbmax + (size_t)q0 * nql, nullptr, nql, sqb, S, p.q_count, c.k, floor_a,
+                                      floor_b, c.st));
+            p.quarter_begin = n_a;
+            p.quarter_end = 0;
+            p.floors = floor_b;
+        }
+        OSK_HIP(launch(nullptr, launch_ev_stop(v, q0, c.nq, kWideQ)));
+    }
+    return OSK_OK;
+}
+
+// The 6-bit tier, one query: pilot → streaming pass over the 6-bit codes → int8 re-bound of the rows that
+// passed (launch_sq6_scan); sq6_prep reserved and the fused prep filled its query form.
+int32_t scan_sq6(const Sq8Call& c, const Sq8Plan& plan, Sq8Lists& out) {
+    osk_view* v = c.v;
+    Sq6Params p{};
+    int32_t rc = sq8_lists(c, v->n_tiles, kSq6ScanR, p, out);
+    if (rc) return rc;
+    OSK_HIP(v->ws_cand6.reserve(sizeof(uint2) * (size_t)p.n_lists * kSq6Cap));
+    OSK_HIP(v->ws_cnt6.reserve(sizeof(int32_t) * (size_t)c.nq * p.n_lists));
+    p.rows6 = v->d_sq6_rows.as<const void*>();
+    p.aux6 = v->d_sq6_aux.as<const float4*>();
+    p.q6 = v->ws_q6.as<int4>();
+    p.qc6 = v->ws_qc6.as<float4>();
+    p.floor = v->ws_floor.as<uint32_t>();
+    p.tile_order = v->d_tile_order.as<int32_t>();
+    p.rb_cus = view_cus(v);   // (the persistent re-bound's grid: 4 workgroups per CU)
+    p.n_segs = (int)v->segs.size();
+    p.rb_stride = g_tuning.sq6_rebound_stride;
+    p.rb_retest = g_tuning.sq6_rebound_retest;
+    p.rb_wg_per_cu = g_tuning.sq6_rebound_wgs;
+    p.cand6 = v->ws_cand6.as<uint2>();
+    p.cnt6 = v->ws_cnt6.as<int32_t>();
+    p.cap6 = kSq6Cap;
+    p.seg_rebound = plan.probe6 ? v->d_seg_rebound.as<unsigned long long>() : nullptr;
+    sq8_chunk(v, p, 0, 1, c.nq);
+    OSK_HIP(launch_sq6_scan(p, v->dim, c.st, launch_ev_start(v, 0), launch_ev_stop(v, 0, c.nq)));
+    // a segment may still turn the tier off: its free waits for this launch
+    return plan.probing ? sq6_track_launch(v, c.st) : OSK_OK;
+}
+
+// Settle the lists a scan reported: per slice of kSliceLists lists (sq8_settle → sq8_settle_merge), or per
+// (shard, query) for the wide scans (sq8_settle_wide).
+int32_t sq8_settle_lists(const Sq8Call& c, const Sq8Lists& lists) {
+    osk_view* v = c.v;
+    OSK_HIP(v->ws_part.reserve(sizeof(uint64_t) * (size_t)c.nq * lists.n_slices * c.k));
     SettleParams sp{};
-    sp.slices = gather ? v->d_gslices.as<int4>() : v->d_slices.as<int4>();
-    sp.shard_slice_begin = gather ? v->d_gshard_slice_begin.as<int32_t>() : v->d_shard_slice_begin.as<int32_t>();
-    sp.tiles = v->d_tiles.as<TileDev>();
-    sp.gtiles = p.gtiles;
-    sp.comp = p.comp;
-    sp.scnt = p.scnt;
-    sp.gather_min = p.gather_min;   // the scan's split, exactly
-    sp.accept = d_accept;
+    sp.slices = lists.slices;
+    sp.shard_slice_begin = lists.shard_slice_begin;
+    sp.tiles = lists.tiles;
+    sp.gather = lists.gather;   // the scan's split, exactly
+    sp.accept = c.d_accept;
     sp.part = v->ws_part.as<uint64_t>();
-    sp.n_slices = n_slices;
+    sp.n_slices = lists.n_slices;
     sp.segs = v->d_segs.as<SegDev>();
     sp.seg_vrow = v->d_seg_vrow.as<int64_t>();
-    sp.cand = p.cand;
-    sp.cand_lb = p.cand_lb;
-    sp.list_lbmax = p.list_lbmax;
+    sp.cand = v->ws_sq8cand.as<uint64_t>();
+    sp.cand_lb = v->ws_sq8lb.as<uint32_t>();
+    sp.list_lbmax = v->ws_lbmax.as<uint32_t>();
     sp.q = v->ws_q.p;
     sp.qnorm = v->ws_qnorm.as<float>();
-    sp.shard_keys = d_shard_keys;
-    sp.shard_counts = d_shard_counts;
+    sp.shard_keys = c.d_shard_keys;
+    sp.shard_counts = c.d_shard_counts;
     sp.flags = v->ws_flags.as<int>();
     sp.counters = v->d_counters.as<unsigned long long>();
-    sp.n_lists = 4 * n_scan_tiles;
-    sp.scan_R = use_mfma ? kMfmaScanR : use6 ? kSq6ScanR : 64 / sq8_lanes(u8);
-    sp.n_shards = S;
+    sp.n_lists = lists.n_lists;
+    sp.scan_R = lists.scan_R;
+    sp.n_shards = v->n_shards;
     sp.n_segs = (int)v->segs.size();
     sp.units = v->units;
-    sp.k = k;
+    sp.k = c.k;
     sp.sim = v->sim;
     sp.force_fail = g_tuning.sq8_force_fallback;
     if (g_tuning.settle_trace) {
-        OSK_HIP(v->ws_trace.reserve(sizeof(unsigned long long) * 8 * (size_t)nq * n_slices));
+        OSK_HIP(v->ws_trace.reserve(sizeof(unsigned long long) * 8 * (size_t)c.nq * lists.n_slices));
         sp.trace = v->ws_trace.as<unsigned long long>();
     }
-    if (use_wide) {
-        sp.tiles = v->d_wtiles.as<TileDev>();
-        sp.shard_tile_begin = v->d_wshard_tile_begin.as<int32_t>();
-        OSK_HIP(launch_sq8_settle_wide(v->cfg, nq, sp, st));
-    } else {
-        OSK_HIP(launch_sq8_settle(v->cfg, nq, sp, st));
+    sp.shard_tile_begin = lists.wide_shard_tile_begin;
+    if (lists.wide_shard_tile_begin)
+        OSK_HIP(launch_sq8_settle_wide(v->cfg, c.nq, sp, c.st));
+    else
+        OSK_HIP(launch_sq8_settle(v->cfg, c.nq, sp, c.st));
+    return OSK_OK;
+}
+
+// ws_q / ws_qnorm are reserved by the caller; wide_pick: sq8_wide_pick for this call.
+int32_t sq8_search(osk_view* v, const void* d_queries, int nq, int k, int UP, const uint64_t* const* d_accept,
+                   uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st,
+                   bool wide_pick) {
+    const Sq8Call c{v, nq, k, d_accept, d_shard_keys, d_shard_counts, d_visited, st};
+    int32_t rc = ensure_sq8(v, st);
+    if (rc || (rc = fold_probe(v, st)) != OSK_OK) return rc;
+    std::shared_lock<std::shared_mutex> tier_lock(g_sq6_free_mu, std::defer_lock);
+    const Sq8Plan plan = sq8_decide(v, nq, d_accept != nullptr, wide_pick, tier_lock);
+    if ((rc = sq8_prep_queries(c, d_queries, UP, plan)) != OSK_OK) return rc;
+    Sq8Lists lists{};
+    switch (plan.strategy) {
+        case Sq8Strategy::kValu: rc = scan_valu(c, plan.gather, lists); break;
+        case Sq8Strategy::kMfma: rc = scan_mfma(c, lists); break;
+        case Sq8Strategy::kWide: rc = scan_wide(c, lists); break;
+        case Sq8Strategy::kSq6: rc = scan_sq6(c, plan, lists); break;
     }
+    if (rc || (rc = profile_end(v, st, false)) != OSK_OK) return rc;
+    if ((rc = sq8_settle_lists(c, lists)) != OSK_OK) return rc;
     v->sq8_calls += 1;
-    v->sq8w_calls += use_wide ? 1 : 0;
-    v->sq6_calls += use6 ? 1 : 0;
-    if (probe6) {   // read back asynchronously: a later call folds it (fold_probe), nothing waits here
-        OSK_HIP(hipMemcpyAsync(v->h_seg_rebound.p, v->d_seg_rebound.p, sizeof(unsigned long long) * ns,
+    v->sq8w_calls += plan.strategy == Sq8Strategy::kWide ? 1 : 0;
+    v->sq6_calls += plan.strategy == Sq8Strategy::kSq6 ? 1 : 0;
+    if (plan.probe6) {   // read back asynchronously: a later call folds it (fold_probe), nothing waits here
+        OSK_HIP(hipMemcpyAsync(v->h_seg_rebound.p, v->d_seg_rebound.p, sizeof(unsigned long long) * v->segs.size(),
                                hipMemcpyDeviceToHost, st));
         OSK_HIP(hipEventRecord(v->ev_probe, st));
         v->probe_pending = true;
@@ -2078,8 +2173,7 @@ int32_t select_search(osk_view* v, const void* d_queries, int nq, int k, int UP,
         p.out_keys = d_shard_keys + (size_t)q * S * k;
         p.out_counts = d_shard_counts + (size_t)q * S;
         p.visited = q == 0 ? reinterpret_cast<unsigned long long*>(d_visited) : nullptr;
-        OSK_HIP(launch_select_one(p, v->cfg, st, v->profile && q == 0 ? v->ev0 : nullptr,
-                                  v->profile && q == nq - 1 ? v->ev1 : nullptr));
+        OSK_HIP(launch_select_one(p, v->cfg, st, launch_ev_start(v, q), launch_ev_stop(v, q, nq, 1)));
     }
     v->sel_calls += 1;
     return OSK_OK;
@@ -2226,11 +2320,11 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
     double R = 0.0;
     for (const osk_seg* sg : v->segs) R += (double)sg->n_rows;
     const int u8v = (v->dim + 15) / 16;
-    const double sq8_us = sq8_wide_pick(v, nq, d_accept != nullptr) ? sq8_wide_us(R, nq, u8v)
-                                                                      : sq8_narrow_us(R, nq, u8v, v->dim);
+    const bool wide_pick = sq8_wide_pick(v, nq, d_accept != nullptr);
+    const double sq8_us = wide_pick ? sq8_wide_us(R, nq, u8v) : sq8_narrow_us(R, nq, u8v, v->dim);
     const double bf_us = (double)((nq + 255) / 256) * (R * (0.153 + 0.00119 * v->dim) * 1e-3 + 325.0);
     const bool blocks_cheaper = bf_us * 100.0 <= sq8_us * (double)g_tuning.sq8_cost_pct &&
-                                !(g_tuning.sq8_wide_force && sq8_wide_pick(v, nq, d_accept != nullptr));
+                                !(g_tuning.sq8_wide_force && wide_pick);
     bool batched = false, prefilter = false, select = false;
     auto choose = [&]() {
         const bool sq8_ok = sq8_on && k <= kKQ - 4;
@@ -2264,7 +2358,7 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
         rc = select_search(v, d_queries, nq, k, UP, d_accept, d_shard_keys, d_shard_counts, d_visited, st, sq8_on);
         if (rc == OSK_OK) rc = profile_end(v, st, false);
     } else if (prefilter) {
-        rc = sq8_search(v, d_queries, nq, k, UP, d_accept, d_shard_keys, d_shard_counts, d_visited, st);
+        rc = sq8_search(v, d_queries, nq, k, UP, d_accept, d_shard_keys, d_shard_counts, d_visited, st, wide_pick);
     } else if (batched) {
         // |q|² in the device lane layout: approx transforms, the re-score (COSINE) and the bound
         OSK_HIP(launch_row_norms_f32(v->ws_q.as<float4>(), nq, UP, v->cfg, v->ws_qnorm.as<float>(), st));
@@ -2325,7 +2419,7 @@ int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const 
         p.maybe = v->ws_thr_maybe.as<uint64_t>();
         p.rows8 = v->d_sq8_rows.as<const int4*>();
         p.aux = v->d_sq8_aux.as<const float4*>();
-        p.settled = v->d_counters.as<unsigned long long>() + 22;
+        p.settled = v->d_counters.as<unsigned long long>() + kCtrThrSettledRows;
         p.gam = v->sq8_gam;
         p.g2 = v->sq8_g2;
         p.units8 = v->units8;
@@ -2718,12 +2812,18 @@ int32_t osk_view_debug_copy(osk_view* v, const char* name, void* host, int64_t b
         *static_cast<int64_t*>(host) = v->sq8_lists_last;
         return OSK_OK;
     }
-    const DevBuf* b = n == "akeys" ? &v->ws_akeys : n == "cand_a" ? &v->ws_cand_a : n == "flags" ? &v->ws_flags
-                    : n == "qsplit" ? &v->ws_qsplit : n == "qnorm" ? &v->ws_qnorm
-                    : n == "sq8cand" ? &v->ws_sq8cand : n == "sq8lb" ? &v->ws_sq8lb : n == "qc" ? &v->ws_qc
-                    : n == "settle_trace" ? &v->ws_trace
-                    : n == "sel_lb" ? &v->ws_sel_lb : n == "sel_ub" ? &v->ws_sel_ub
-                    : nullptr;
+    static const struct {
+        const char* name;
+        DevBuf osk_view::*buf;
+    } kBuffers[] = {
+        {"akeys", &osk_view::ws_akeys},     {"cand_a", &osk_view::ws_cand_a},       {"flags", &osk_view::ws_flags},
+        {"qsplit", &osk_view::ws_qsplit},   {"qnorm", &osk_view::ws_qnorm},         {"sq8cand", &osk_view::ws_sq8cand},
+        {"sq8lb", &osk_view::ws_sq8lb},     {"qc", &osk_view::ws_qc},               {"settle_trace", &osk_view::ws_trace},
+        {"sel_lb", &osk_view::ws_sel_lb},   {"sel_ub", &osk_view::ws_sel_ub},
+    };
+    const DevBuf* b = nullptr;
+    for (const auto& e : kBuffers)
+        if (n == e.name) b = &(v->*e.buf);
     OSK_REQUIRE(b != nullptr, "unknown buffer");
     OSK_REQUIRE((size_t)bytes <= b->cap, "bytes exceed the buffer");
     OSK_HIP(hipDeviceSynchronize());   // the last search may be on any stream
@@ -2785,50 +2885,56 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
         *value = (int64_t)c;
         return OSK_OK;
     }
-    const bool dev = n == "sq8_fallback_queries" || n == "sq8_rescored_rows" || n == "sq8_exact_tiles" ||
-                     n == "sq6_rebound_rows" || n == "sq8_wide_events" || n == "sq8_wide_pairs" ||
-                     n == "sq8_wide_wait_cycles" || n == "sq8_wide_slow_steps" || n == "sq8_wide_loop_cycles" ||
-                     n == "sq8_wide_slow_cycles" || n == "sq8_wide_drain_cycles" ||
-                     n == "sq6_rebound_gathered_rows" || n == "sq6_rebound_passes" ||
-                     n == "sq6_rebound_max_wg_cycles" || n == "sq8_rows_total_cycles" || n == "sq8_rows_setup_cycles" ||
-                     n == "sq8_rows_quarter_end_cycles" || n == "sq8_rows_first_wait_cycles" ||
-                     n == "sq8_rows_setup_barrier_cycles" || n == "sq8_rows_setup_fragment_cycles" ||
-                     n == "threshold_sq8_settled_rows";
-    OSK_REQUIRE(dev || n == "mfma_calls" || n == "mfma_fallback_queries" || n == "sq8_calls" || n == "sq6_calls" ||
-                    n == "select_calls" || n == "sq8_wide_calls" || n == "threshold_calls" || n == "nested_calls" ||
-                    n == "threshold_sq8_calls",
-                "unknown counter: " + n);
-    // summed over the view and the replicas its host entries leased
+    // every other counter: a device slot (Ctr) or a host member of the view, summed over the view and the
+    // replicas its host entries leased
+    static const struct {
+        const char* name;
+        int slot;                        // device slot, or -1:
+        int64_t osk_view::*host;         // the host member
+    } kCounters[] = {
+        {"mfma_calls", -1, &osk_view::mfma_calls},
+        {"mfma_fallback_queries", -1, &osk_view::mfma_fallback_queries},
+        {"sq8_calls", -1, &osk_view::sq8_calls},
+        {"sq6_calls", -1, &osk_view::sq6_calls},
+        {"select_calls", -1, &osk_view::sel_calls},
+        {"sq8_wide_calls", -1, &osk_view::sq8w_calls},
+        {"threshold_calls", -1, &osk_view::thr_calls},
+        {"threshold_sq8_calls", -1, &osk_view::thr_sq8_calls},
+        {"nested_calls", -1, &osk_view::nest_calls},
+        {"sq8_fallback_queries", kCtrFallbackQueries, nullptr},
+        {"sq8_rescored_rows", kCtrRescoredRows, nullptr},
+        {"sq8_exact_tiles", kCtrExactLists, nullptr},
+        {"sq6_rebound_rows", kCtrSq6ReboundRows, nullptr},
+        {"sq6_rebound_gathered_rows", kCtrSq6GatheredRows, nullptr},
+        {"sq6_rebound_passes", kCtrSq6ReboundPasses, nullptr},
+        {"sq6_rebound_max_wg_cycles", kCtrSq6MaxWgCycles, nullptr},
+        {"sq8_wide_events", kCtrWideEvents, nullptr},
+        {"sq8_wide_pairs", kCtrWidePairs, nullptr},
+        {"sq8_wide_wait_cycles", kCtrWideWaitCycles, nullptr},
+        {"sq8_wide_slow_steps", kCtrWideSlowSteps, nullptr},
+        {"sq8_wide_loop_cycles", kCtrWideLoopCycles, nullptr},
+        {"sq8_wide_slow_cycles", kCtrWideSlowCycles, nullptr},
+        {"sq8_wide_drain_cycles", kCtrWideDrainCycles, nullptr},
+        {"sq8_rows_total_cycles", kCtrRowsTotalCycles, nullptr},
+        {"sq8_rows_setup_cycles", kCtrRowsSetupCycles, nullptr},
+        {"sq8_rows_quarter_end_cycles", kCtrRowsQuarterEndCycles, nullptr},
+        {"sq8_rows_first_wait_cycles", kCtrRowsFirstWaitCycles, nullptr},
+        {"sq8_rows_setup_barrier_cycles", kCtrRowsSetupBarrierCycles, nullptr},
+        {"sq8_rows_setup_fragment_cycles", kCtrRowsSetupFragmentCycles, nullptr},
+        {"threshold_sq8_settled_rows", kCtrThrSettledRows, nullptr},
+    };
+    const auto* ctr = std::find_if(std::begin(kCounters), std::end(kCounters), [&](const auto& e) { return n == e.name; });
+    OSK_REQUIRE(ctr != std::end(kCounters), "unknown counter: " + n);
     int64_t sum = 0;
     for (osk_view* s : slot_views(v)) {
         std::lock_guard<std::mutex> lk(s->mu);
-        if (dev) {
-            if (!s->d_counters.p) continue;
-            unsigned long long c[24];
+        if (ctr->host) {
+            sum += s->*ctr->host;
+        } else if (s->d_counters.p) {
+            unsigned long long c = 0;
             OSK_HIP(hipDeviceSynchronize());   // the last search may be on any stream
-            OSK_HIP(hipMemcpy(c, s->d_counters.p, sizeof(c), hipMemcpyDeviceToHost));
-            // [4] … [8]: the wide kernel's insertion events, quick-test passes, wave 0's shader clocks in the
-            // step loop's waits [6] and whole loop [8], and the wave-steps that took the slow path [7] (testing build)
-            sum += (int64_t)(n == "sq8_fallback_queries" ? c[0] : n == "sq8_rescored_rows" ? c[1]
-                             : n == "sq8_exact_tiles" ? c[2] : n == "sq6_rebound_rows" ? c[3]
-                             : n == "sq8_wide_events" ? c[4] : n == "sq8_wide_pairs" ? c[5]
-                             : n == "sq8_wide_wait_cycles" ? c[6] : n == "sq8_wide_slow_steps" ? c[7]
-                             : n == "sq8_wide_loop_cycles" ? c[8] : n == "sq8_wide_slow_cycles" ? c[9]
-                             : n == "sq8_wide_drain_cycles" ? c[10] : n == "sq6_rebound_gathered_rows" ? c[11]
-                             : n == "sq6_rebound_passes" ? c[12] : n == "sq6_rebound_max_wg_cycles" ? c[13]
-                             // [16] … [19]: sq8_wide_rows, wave 0's shader clocks per workgroup summed: the whole
-                             // kernel, its setup (to the first quarter), the quarter ends (publish, barriers, drain,
-                             // flush, next constants), the waits for each quarter's first group (testing build)
-                             : n == "sq8_rows_total_cycles" ? c[16] : n == "sq8_rows_setup_cycles" ? c[17]
-                             : n == "sq8_rows_quarter_end_cycles" ? c[18] : n == "sq8_rows_first_wait_cycles" ? c[19]
-                             : n == "sq8_rows_setup_barrier_cycles" ? c[20]
-                             : n == "sq8_rows_setup_fragment_cycles" ? c[21]
-                             : c[22]);   // [22]: rows thr_settle_f32 re-scored (threshold_sq8_settled_rows)
-        } else {
-            sum += n == "mfma_calls" ? s->mfma_calls : n == "mfma_fallback_queries" ? s->mfma_fallback_queries
-                 : n == "sq8_calls" ? s->sq8_calls : n == "sq6_calls" ? s->sq6_calls
-                 : n == "sq8_wide_calls" ? s->sq8w_calls : n == "threshold_calls" ? s->thr_calls
-                 : n == "threshold_sq8_calls" ? s->thr_sq8_calls : n == "nested_calls" ? s->nest_calls : s->sel_calls;
+            OSK_HIP(hipMemcpy(&c, s->d_counters.as<unsigned long long>() + ctr->slot, sizeof(c), hipMemcpyDeviceToHost));
+            sum += (int64_t)c;
         }
     }
     *value = sum;

@@ -118,9 +118,43 @@ constexpr int kKQ = 16;              // per-tile candidate list of the prefilter
 constexpr int kSliceLists = 32;      // wave lists per settle workgroup (32 × kKQ = 512 entries)
 constexpr int kLGroupLists = 4096;   // lists whose best lower bounds define one settle threshold
 
-struct Sq8Params {
+// Slots of a view's device counters (osk_view::d_counters), named after what each counts; osk_view_counter
+// maps the public counter names to them.  Slots 14 and 15 are unused (saved profiles keep their meaning).
+enum Ctr : int {
+    kCtrFallbackQueries = 0,       // settle: queries with an exactly re-scanned list
+    kCtrRescoredRows = 1,          // settle: rows re-scored
+    kCtrExactLists = 2,            // settle: lists re-scanned exactly
+    kCtrSq6ReboundRows = 3,        // sq6_rebound: rows re-bounded on int8
+    // the wide kernels (testing build): insertion events, quick-test passes, wave 0's shader clocks in the step
+    // loop's waits, the wave-steps that took the slow path, the whole loop's, the slow path's and the drain's clocks
+    kCtrWideEvents = 4,
+    kCtrWidePairs = 5,
+    kCtrWideWaitCycles = 6,
+    kCtrWideSlowSteps = 7,
+    kCtrWideLoopCycles = 8,
+    kCtrWideSlowCycles = 9,
+    kCtrWideDrainCycles = 10,
+    kCtrSq6GatheredRows = 11,      // sq6_rebound: rows gathered from the int8 copy
+    kCtrSq6ReboundPasses = 12,     // ...its 8-row passes
+    kCtrSq6MaxWgCycles = 13,       // ...the slowest workgroup's clocks
+    // sq8_wide_rows (testing build), wave 0's shader clocks per workgroup summed: the whole kernel, its setup (to
+    // the first quarter), the quarter ends (publish, barriers, drain, flush, next constants), the waits for each
+    // quarter's first group, the setup to its first barrier, then the fragments' arrival
+    kCtrRowsTotalCycles = 16,
+    kCtrRowsSetupCycles = 17,
+    kCtrRowsQuarterEndCycles = 18,
+    kCtrRowsFirstWaitCycles = 19,
+    kCtrRowsSetupBarrierCycles = 20,
+    kCtrRowsSetupFragmentCycles = 21,
+    kCtrThrSettledRows = 22,       // thr_settle_f32: rows re-scored
+    kCtrCount = 24
+};
+
+// What every prefilter scan kernel takes; each strategy's kernels take a struct derived from it, so a kernel
+// cannot name another strategy's field.
+struct Sq8Common {
     const SegDev* segs;
-    const TileDev* tiles;
+    const TileDev* tiles;            // the view's scan tiles (row ranges of one segment each)
     const uint64_t* const* accept;
     const int4* const* rows8;        // per segment: int8 rows [n_rows][units8] 16-B units
     const float4* const* aux;        // per segment: {scale, scale·|q8|, |x − scale·q8|, |x|²} per row
@@ -132,7 +166,7 @@ struct Sq8Params {
     uint32_t* cand_lb;               // [nq][n_lists][kKQ] sortable lower-bound scores
     uint32_t* list_lbmax;            // [nq][n_lists] best lower bound of each list (0 = empty)
     unsigned long long* visited;
-    int n_tiles;
+    int n_tiles;                     // tiles of the table the launch walks: the scan, gather or wide tiles
     int n_lists;                     // 4 · n_tiles
     int q0;
     int q_count;
@@ -141,59 +175,83 @@ struct Sq8Params {
     float gam;                       // fp32 dot rounding: |dot_dev − x·b| ≤ gam·(|x|² + |b|²)
     float g2;                        // fp32 d² rounding:  |d²_dev − d²| ≤ g2·d²
     float cos_slack;                 // COSINE quick test: norm-order slack
-    // sq8_mfma only.  pilot = 1: each wave scores just its first 16 (accepted) rows; the tile's top k
-    // lower-bound keys per query go to pilot_keys [q_count][n_tiles][k]; merged per (query, shard)
-    // into thr_keys [q_count][n_shards][k] / thr_counts.  pilot = 0: the k-th best sampled
-    // lower bound T of the (query, shard) is a floor under every wave list's quick threshold: a row
-    // with ub < T ≤ the shard's k-th best lower bound scores below the shard's k-th exact score.
-    int pilot;
-    const int4* const* rows8t;       // sq8_mfma: per segment, the tiled int8 copy (launch_sq8_tile)
-    int nt;                          // sq8_mfma: non-temporal row loads (A/B knob sq8_mfma_nt)
     int ablate;                      // A/B timing only (results wrong): 1 skip the epilogue, 2 skip the MFMAs
-    int ring_slots;                  // sq8_mfma: > 1 = LDS-DMA ring of this many 16-row groups per wave
-                                     // (unfiltered, ≤ 256 dims; tune sq8_mfma_ring), 0 = register loads
+    unsigned long long* counters;    // the view's device counters [kCtrCount]
     int k;
     int n_shards;
-    uint64_t* pilot_keys;
-    const uint64_t* thr_keys;
-    const int32_t* thr_counts;
-    // gather mode (filtered sq8_scan, osk_filter.hip compaction): the grid runs over gather tiles
-    // {seg, shard, j, nj} — tile j of nj over segment seg's scnt[seg] accepted ordinals at
-    // comp[seg_vrow[seg] …] — instead of `tiles`; null = the row-range tiles
+};
+
+// Gather mode (filtered sq8_scan, osk_filter.hip compaction): the grid runs over gather tiles
+// {seg, shard, j, nj} — tile j of nj over segment seg's scnt[seg] accepted ordinals at
+// comp[seg_vrow[seg] …] — instead of `tiles`; gtiles null = the row-range tiles.  The settle takes the
+// scan's split, exactly.
+struct GatherSplit {
     const int4* gtiles;
     const uint32_t* comp;
     const int32_t* scnt;
     int gather_min;                  // at most one gather tile per this many accepted rows of a segment
-    // sq6_scan (osk_sq6.hip): per segment, the 6-bit tiled codes and their bound terms; the query's nibble
-    // split ([8C half-chunks][bh 4 dwords, bl 4 dwords]) and its 6-bit bound terms; the per-(query, shard)
-    // floor buckets [q][n_shards][kFloorBuckets] (sortable lower bounds; rows8 / aux / q8 / qc are the
-    // int8 re-bound of the rows that pass the 6-bit test)
+};
+
+struct Sq8ScanParams : Sq8Common {   // sq8_scan
+    GatherSplit gather;
+};
+
+struct Sq8MfmaParams : Sq8Common {   // sq8_mfma
+    const int4* const* rows8t;       // per segment, the tiled int8 copy (launch_sq8_tile)
+    // pilot = 1: each wave scores just its first 16 (accepted) rows; the tile's top k lower-bound keys per
+    // query go to pilot_keys [q_count][n_tiles][k]; merged per (query, shard) into thr_keys
+    // [q_count][n_shards][k] / thr_counts.  pilot = 0: the k-th best sampled lower bound T of the (query,
+    // shard) is a floor under every wave list's quick threshold: a row with ub < T ≤ the shard's k-th best
+    // lower bound scores below the shard's k-th exact score.
+    uint64_t* pilot_keys;
+    const uint64_t* thr_keys;
+    const int32_t* thr_counts;
+    int ring_slots;                  // > 1 = LDS-DMA ring of this many 16-row groups per wave (unfiltered,
+                                     // ≤ 256 dims; tune sq8_mfma_ring), 0 = register loads
+    int pilot;
+    int nt;                          // non-temporal row loads (A/B knob sq8_mfma_nt)
+};
+
+struct Sq8WideParams : Sq8Common {   // sq8_wide, sq8_wide_rows
+    int pilot;                       // 1: each quarter's first rows only → pilot_keys [q][4·n_tiles]
+    uint64_t* pilot_keys;
+    int pilot_rows;                  // pilot: rows bounded per quarter (0 = kWidePilotRows)
+    const int4* const* rows8w;       // per segment, the wide copy: one scale per 16-row group (launch_sq8w_build)
+    const float4* const* auxt;       // ...and the 16-row groups' bound terms
+    const TileDev* wtiles;           // the wide kernels' own tile table [n_tiles] (ensure_sq8w)...
+    const int32_t* tile_order;       // ...and its dispatch order (tiles interleaved over shards)
+    int wide_grid;                   // persistent workgroups (the device's CUs)
+    int quarter_begin, quarter_end;  // the launch's quarters in tile order (end 0: all)
+    int wide_defer;                  // sq8_wide: defer insertions to the quarter's end when LDS allows (tune)
+    int wide_qcap;                   // entries per wave's deferred queue (0: sq8_wide immediate, sq8_wide_rows what
+                                     // LDS leaves); the launchers pass the kernel what fits
+    const uint32_t* floors;          // [q_count][n_shards] floor score (sortable bits; 0 = none)
+    const float4* quarter_bm;        // [4·n_tiles] the quarters' row maxima (launch_wide_quarter_max)
+    const void* wide_qtable;         // [4·n_tiles] the quarters' descriptors in tile order (null: computed)
+    int wide_claim;                  // sq8_wide_rows: waves claim groups from a per-quarter counter (0: fixed interleave)
+};
+
+// sq6_pilot, sq6_scan, sq6_rebound (osk_sq6.hip): per segment, the 6-bit tiled codes and their bound terms; the
+// query's nibble split ([8C half-chunks][bh 4 dwords, bl 4 dwords]) and its 6-bit bound terms; the per-(query,
+// shard) floor buckets [q][n_shards][kFloorBuckets] (sortable lower bounds; rows8 / aux / q8 / qc are the int8
+// re-bound of the rows that pass the 6-bit test)
+struct Sq6Params : Sq8Common {
     const void* const* rows6;
     const float4* const* aux6;
     const int4* q6;
     const float4* qc6;
     uint32_t* floor;
-    unsigned long long* counters;    // sq6_scan adds its int8 re-bounds to [3] (SettleParams::counters)
     unsigned long long* seg_rebound; // calibration probes: the int8 re-bounds per segment [n_segs], or null
-    const int32_t* tile_order;       // sq6_scan: the tile of each workgroup (tiles interleaved over shards)
+    const int32_t* tile_order;       // the tile of each workgroup (tiles interleaved over shards)
     uint2* cand6;                    // sq6_scan → sq6_rebound: per list, the rows that passed the 6-bit test
                                      // {row, its 6-bit test value (osk_sq6.hip cand6_value)}
     int32_t* cnt6;                   // [q][n_lists] their count (> cap6: overflowed)
     int cap6;
-    const float4* const* auxt;       // sq8_wide: per segment, the 16-row groups' bound terms (launch_sq8w_build)
-    int wide_grid;                   // sq8_wide: persistent workgroups (the device's CUs)
+    int rb_cus;                      // sq6_rebound: the device's CUs (its persistent grid is workgroups per CU × this)
     int n_segs;                      // sq6_rebound: the view's segments (LDS per-segment counts when ≤ 64)
     int rb_stride;                   // sq6_rebound: 1 = wave gw takes lists gw, gw + W, … (tune sq6_rebound_stride)
     int rb_wg_per_cu;                // sq6_rebound: workgroups per CU (0 = as many as fit; tune sq6_rebound_wgs)
     int rb_retest;                   // sq6_rebound: re-test candidates at the 6-bit level against the final floor
-    int quarter_begin, quarter_end;  // sq8_wide: the launch's quarters in tile order (end 0: all)
-    int pilot_rows;                  // sq8_wide pilot: rows bounded per quarter (0 = kWidePilotRows)
-    int wide_defer;                  // sq8_wide: defer insertions to the quarter's end when LDS allows (tune)
-    int wide_qcap;                   // (set by launch_sq8_wide: entries per wave's deferred queue, 0 = immediate)
-    const uint32_t* floors;          // sq8_wide: [q_count][n_shards] floor score (sortable bits; 0 = none)
-    const float4* quarter_bm;        // sq8_wide: [4·n_tiles] the quarters' row maxima (launch_wide_quarter_max)
-    const void* wide_qtable;         // sq8_wide: [4·n_tiles] the quarters' descriptors in tile order (null: computed)
-    int wide_claim;                  // sq8_wide_rows: waves claim groups from a per-quarter counter (0: fixed interleave)
 };
 
 struct SettleParams {
@@ -207,8 +265,7 @@ struct SettleParams {
     uint64_t* shard_keys;            // [nq][n_shards][k]
     int32_t* shard_counts;
     int* flags;                      // [nq] set when some list of the query was re-scanned exactly
-    unsigned long long* counters;    // [0] queries with an exactly re-scanned list, [1] rows re-scored,
-                                     // [2] lists re-scanned exactly
+    unsigned long long* counters;    // the view's device counters [kCtrCount] (its first three)
     const int4* slices;              // [n_slices] {list_begin, list_end, L-group begin, L-group end}
     const int32_t* shard_slice_begin;// [n_shards + 1]
     const TileDev* tiles;            // the view's tiles (exact re-scan of an overflowed list)
@@ -223,10 +280,7 @@ struct SettleParams {
     int k;
     int sim;
     int force_fail;                  // tests: re-scan every list exactly
-    const int4* gtiles;              // gather mode (see Sq8Params): lists are gather tile·4 + wave
-    const uint32_t* comp;
-    const int32_t* scnt;
-    int gather_min;
+    GatherSplit gather;              // gather mode: lists are gather tile·4 + wave
     unsigned long long* trace;       // A/B only: per (query, slice) 8 slots of phase timestamps, or null
     const int32_t* shard_tile_begin; // sq8_settle_wide: [n_shards + 1] (a shard's lists are 4·[begin, end))
 };
@@ -339,7 +393,7 @@ hipError_t launch_sq8_quantize(const float4* x, int64_t n, int units, int pitch,
                                float4* aux, int mode, hipStream_t s, int* out_of_range = nullptr);
 // ev_start / ev_stop (optional): stamped by the kernel's own dispatch packet (hipExtLaunchKernelGGL),
 // so timing a launch adds no marker packets (and no gaps) to the stream
-hipError_t launch_sq8_scan(int nq, const Sq8Params& p, hipStream_t s, hipEvent_t ev_start = nullptr,
+hipError_t launch_sq8_scan(int nq, const Sq8ScanParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr);
 int sq8_lanes(int units8);         // lanes per row of the int8 scan
 // int8 MFMA prefilter scan: ≤ kMfmaQueries queries per launch, rows ≤ 1024 int8 dims (sq8_mfma_supported)
@@ -351,7 +405,7 @@ int sq8_ring_slots(int units8, int qb, int want);   // sq8_mfma LDS-DMA ring dep
 // row-major int8 rows → blocks of 16 rows × ks slabs of 1 KiB (row r of a block at r·64 B; zero past
 // the last row and past units8)
 hipError_t launch_sq8_tile(const void* q8, int64_t n_rows, int units8, int ks, void* out, hipStream_t s);
-hipError_t launch_sq8_mfma(const Sq8Params& p, hipStream_t s, hipEvent_t ev_start = nullptr,
+hipError_t launch_sq8_mfma(const Sq8MfmaParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr);
 // int8 MFMA prefilter for large batches (osk_sq8w.hip): kWideQ queries per launch, 32 per wave, rows
 // ≤ 768 int8 dims, unfiltered.  Persistent: one workgroup of 8 waves per CU streams its share of the
@@ -367,10 +421,10 @@ constexpr int kWidePilotSample = 65536;      // ...raised to sample at least thi
 constexpr int kAuxGroupF4 = 22;                 // float4 per 16-row group of the tiled bound terms
 int sq8_wide_supported(int units8);
 int sq8_wide_ks(int units8);                    // its 64-dim slabs per row: 2, 4, 8 or 12
-hipError_t launch_sq8_wide(const Sq8Params& p, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+hipError_t launch_sq8_wide(const Sq8WideParams& p, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // the wide kernel's main passes for ≤ 128-dim rows without a step barrier (osk_sq8w.hip sq8_wide_rows)
 bool sq8_wide_rows_supported(int u8);
-hipError_t launch_sq8_wide_rows(const Sq8Params& p, hipStream_t s, hipEvent_t ev_start = nullptr,
+hipError_t launch_sq8_wide_rows(const Sq8WideParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
                                 hipEvent_t ev_stop = nullptr);
 #ifdef OSK_TESTING
 hipError_t launch_glds_probe(const int4* src, int4* out, hipStream_t s);   // (osk_testing_glds_probe)
@@ -420,7 +474,7 @@ constexpr int kFloorStride = 16;        // one 64-B line per bucket (uint32 unit
 constexpr int kSq6Probes = 4;            // calibration probes of the 6-bit tier per segment (osk_seg::sq6_state)
 constexpr int kSq6Cap = 256;             // candidate rows per list between the 6-bit pass and the int8 re-bound
 hipError_t launch_sq6_quantize(const float4* x, int64_t n, int units, int dim, void* out, float4* aux, hipStream_t s);
-hipError_t launch_sq6_scan(const Sq8Params& p, int dim, hipStream_t s, hipEvent_t ev_start = nullptr,
+hipError_t launch_sq6_scan(const Sq6Params& p, int dim, hipStream_t s, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr);
 hipError_t launch_sq8_settle(int cfg, int nq, const SettleParams& p, hipStream_t s);
 

@@ -196,7 +196,7 @@ struct osk_view {
     bool sq8_range_ok = true;   // (with sq8_ready) no segment has a row outside the certificate's range
     int units8 = 0;
     float sq8_gam = 0.f, sq8_g2 = 0.f, sq8_cos_slack = 0.f;
-    osk::DevBuf d_sq8_rows, d_sq8_aux, d_counters;   // counters: SettleParams::counters
+    osk::DevBuf d_sq8_rows, d_sq8_aux, d_counters;   // counters: [kCtrCount] slots (osk_internal.h Ctr)
     osk::DevBuf d_sq8_rows_t;                         // per segment: tiled int8 copy (sq8_mfma)
     osk::DevBuf d_sq8_rows_w;                         // per segment: the wide kernel's group-scaled copy
     osk::DevBuf d_sq8_auxt, d_shard_quarter_begin;    // per segment: its tiled bound terms (sq8_wide); 4·shard_tile_begin

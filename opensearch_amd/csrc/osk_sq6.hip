@@ -182,7 +182,7 @@ __device__ __forceinline__ float floor_lb_score(int sim, float lo, float hi, flo
 // of its range (the 6-bit pass's split) on the int8 copy (16 lanes per row, exact device-order norms)
 // and raises its floor bucket (list mod 64) to the best of them.
 template <int C>
-__global__ __launch_bounds__(kBlock) void sq6_pilot(Sq8Params p) {
+__global__ __launch_bounds__(kBlock) void sq6_pilot(Sq6Params p) {
     constexpr int R = 8;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: scalar loop control
     const int cg = lane >> 4, ct = lane & 15;
@@ -260,7 +260,7 @@ __device__ __forceinline__ bool cand6_keep(int sim, float v, float tq) {
 // k-th best exact score: it cannot enter the top k.  The best 6-bit lower bound among a wave's passing
 // rows raises its floor bucket as the pass goes (a distinct row per bucket, as for the pilot's).
 template <int C, int U>
-__global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq8Params p) {   // ≤ 128 VGPRs: 4 waves/SIMD
+__global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq6Params p) {   // ≤ 128 VGPRs: 4 waves/SIMD
     constexpr int R = 8;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: scalar loop control
     const int t = lane & 7, g = lane >> 3;
@@ -435,7 +435,7 @@ __global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq8Params p) {   // ≤ 12
 // workgroup's counters leave with one global atomic each: same-address atomics queue at L2 (≈ 4 ns apiece;
 // one per wave, 4,096 of them, cost ≈ 16 µs per launch, profiles/r05e/).
 template <int C>
-__global__ __launch_bounds__(kBlock) void sq6_rebound(Sq8Params p) {
+__global__ __launch_bounds__(kBlock) void sq6_rebound(Sq6Params p) {
     constexpr int kMaxLds = 64;
     __shared__ uint32_t s_floor[kMaxLds];
     __shared__ unsigned long long s_vis[kMaxLds], s_reb[kMaxLds];
@@ -626,11 +626,11 @@ __global__ __launch_bounds__(kBlock) void sq6_rebound(Sq8Params p) {
     }
     __syncthreads();
     if (threadIdx.x == 0 && p.counters) {
-        if (s_tot[0]) atomicAdd(&p.counters[3], s_tot[0]);
-        if (s_tot[1]) atomicAdd(&p.counters[11], s_tot[1]);   // rows gathered from the int8 copy
+        if (s_tot[0]) atomicAdd(&p.counters[kCtrSq6ReboundRows], s_tot[0]);
+        if (s_tot[1]) atomicAdd(&p.counters[kCtrSq6GatheredRows], s_tot[1]);   // rows gathered from the int8 copy
 #ifdef OSK_TESTING
-        atomicAdd(&p.counters[12], s_tot[2]);   // 8-row passes
-        atomicMax(&p.counters[13], s_tot[3]);   // the slowest workgroup's clocks
+        atomicAdd(&p.counters[kCtrSq6ReboundPasses], s_tot[2]);   // 8-row passes
+        atomicMax(&p.counters[kCtrSq6MaxWgCycles], s_tot[3]);   // the slowest workgroup's clocks
 #endif
     }
     if (seg_lds)
@@ -641,14 +641,14 @@ __global__ __launch_bounds__(kBlock) void sq6_rebound(Sq8Params p) {
 }
 
 // row groups per wave-iteration by C: ≈ 12–14 KiB of loads in flight per wave
-using Sq6Fn = void (*)(Sq8Params);
+using Sq6Fn = void (*)(Sq6Params);
 static const Sq6Fn kSq6[5] = {sq6_scan<2, 4>, sq6_scan<3, 3>, sq6_scan<4, 2>, sq6_scan<5, 1>, sq6_scan<6, 1>};
 static const Sq6Fn kSq6Pilot[5] = {sq6_pilot<2>, sq6_pilot<3>, sq6_pilot<4>, sq6_pilot<5>, sq6_pilot<6>};
 static const Sq6Fn kSq6Rebound[5] = {sq6_rebound<2>, sq6_rebound<3>, sq6_rebound<4>, sq6_rebound<5>, sq6_rebound<6>};
 
 // pilot → streaming pass → int8 re-bound pass; the profiling events bracket the streaming pass, the
 // dominant kernel whose roofline bench.py reports (the pilot and the re-bound read ≈ 2-3 % of its bytes)
-hipError_t launch_sq6_scan(const Sq8Params& p, int dim, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+hipError_t launch_sq6_scan(const Sq6Params& p, int dim, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     const int C = sq6_chunks(dim);
     if (C < 2 || C > 6 || p.q_count != 1 || p.k < 1 || p.k > kKQ || !p.floor || !p.q6 || !p.cand6 || !p.cnt6 ||
         !p.tile_order || p.cap6 < 64 || p.cap6 > kSq6Cap)
@@ -674,7 +674,7 @@ hipError_t launch_sq6_scan(const Sq8Params& p, int dim, hipStream_t s, hipEvent_
         fit_of.store(fit, std::memory_order_relaxed);
     }
     const int per_cu = p.rb_wg_per_cu > 0 ? p.rb_wg_per_cu : fit;
-    const int rb_grid = std::max(1, std::min(p.n_tiles, per_cu * (p.wide_grid > 0 ? p.wide_grid : 256)));
+    const int rb_grid = std::max(1, std::min(p.n_tiles, per_cu * (p.rb_cus > 0 ? p.rb_cus : 256)));
     hipLaunchKernelGGL(rb, dim3(rb_grid), dim3(kBlock), 0, s, p);
     return hipGetLastError();
 }

@@ -323,14 +323,14 @@ __device__ __forceinline__ void gather_wave_range(int64_t cnt, int j, int nj, in
 }
 
 template <int L, int V, int NQ, int U, int MODE = kScanRows>
-__global__ __launch_bounds__(kBlock, NQ == 1 && V <= 3 ? (U > 4 ? 3 : 4) : 1) void sq8_scan(Sq8Params p) {   // ≤ 128 VGPRs: 4 waves/SIMD (U = 8: 3)
+__global__ __launch_bounds__(kBlock, NQ == 1 && V <= 3 ? (U > 4 ? 3 : 4) : 1) void sq8_scan(Sq8ScanParams p) {   // ≤ 128 VGPRs: 4 waves/SIMD (U = 8: 3)
     constexpr int R = 64 / L;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: scalar loop control
     const int t = lane & (L - 1), g = lane / L;
     TileDev tile;
     int4 gt = make_int4(0, 0, 0, 1);
     if constexpr (MODE == kScanGather) {
-        gt = p.gtiles[blockIdx.x];
+        gt = p.gather.gtiles[blockIdx.x];
         tile = TileDev{gt.x, gt.y, 0, 0};
     } else {
         tile = p.tiles[blockIdx.x];
@@ -544,8 +544,8 @@ __global__ __launch_bounds__(kBlock, NQ == 1 && V <= 3 ? (U > 4 ? 3 : 4) : 1) vo
         // 64 at a time (one coalesced index load, then the rows), any segment layout (dense or sparse)
         // (counts and ordinals are clamped to the segment: a corrupt list can never address outside it)
         int64_t eb, ee;
-        gather_wave_range(min<int64_t>(p.scnt[tile.seg], seg.n_rows), gt.z, gt.w, p.gather_min, wave, eb, ee);
-        const uint32_t* __restrict__ C = p.comp + vbase;
+        gather_wave_range(min<int64_t>(p.gather.scnt[tile.seg], seg.n_rows), gt.z, gt.w, p.gather.gather_min, wave, eb, ee);
+        const uint32_t* __restrict__ C = p.gather.comp + vbase;
         for (int64_t e0 = eb; e0 < ee; e0 += 64) {
             const int n = (int)min<int64_t>(64, ee - e0);
             const int pos = lane < n ? (int)min<int64_t>(C[e0 + lane], seg.n_rows - 1) : 0;
@@ -604,7 +604,7 @@ int sq8_lanes(int u8) {   // L of the scan's config (its rows per wave-iteration
     static const int kL[8] = {4, 8, 16, 16, 16, 16, 32, 64};
     return kL[sq8_cfg(u8)];
 }
-using Sq8Fn = void (*)(Sq8Params);
+using Sq8Fn = void (*)(Sq8ScanParams);
 #define OSK_SQ8_ROW(L, V) {sq8_scan<L, V, 1, 4>, sq8_scan<L, V, 2, 4>, sq8_scan<L, V, 4, 4>, sq8_scan<L, V, 8, 2>}
 static const Sq8Fn kSq8[8][4] = {OSK_SQ8_ROW(4, 1),  OSK_SQ8_ROW(8, 1),  OSK_SQ8_ROW(16, 1), OSK_SQ8_ROW(16, 2),
                                  OSK_SQ8_ROW(16, 3), OSK_SQ8_ROW(16, 4), OSK_SQ8_ROW(32, 4), OSK_SQ8_ROW(64, 4)};
@@ -621,12 +621,12 @@ static const Sq8Fn kSq8Gather[8][4] = {OSK_SQ8_GROW(4, 1),  OSK_SQ8_GROW(8, 1), 
 // 0.061 ms (profiles/r06/call11/cfg_small_d*.jsonl): the U = 4 scan's 5 waves per SIMD hide the latency better
 static const Sq8Fn kSq8Deep[3] = {sq8_scan<4, 1, 1, 8>, sq8_scan<8, 1, 1, 8>, sq8_scan<16, 1, 1, 8>};
 
-hipError_t launch_sq8_scan(int nq, const Sq8Params& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+hipError_t launch_sq8_scan(int nq, const Sq8ScanParams& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     const int slot = nq <= 1 ? 0 : nq <= 2 ? 1 : nq <= 4 ? 2 : 3;
     // NQ > 1: the queries and the 4 waves' per-query lists in LDS
     const size_t lds = slot == 0 ? 0 : (size_t)(1 << slot) * (p.units8 * 16 + 4 * kKQ * 12);
     const int c = sq8_cfg(p.units8);
-    const auto fn = p.gtiles ? kSq8Gather[c][slot]
+    const auto fn = p.gather.gtiles ? kSq8Gather[c][slot]
                     : (slot == 0 && c <= 2 && g_tuning.sq8_scan_deep) ? kSq8Deep[c]
                                                                       : kSq8[c][slot];
     if (ev_start || ev_stop)
@@ -690,7 +690,7 @@ struct AuxQ {
 template <int KS, int QB, int NS, int SIM>
 // KS = 2 ring instances are capped at 128 VGPRs: their LDS holds four workgroups per CU, and 4 waves per
 // SIMD need ≤ 128 (C4 b32: 123 VGPRs 2.71 ms, 131 VGPRs 2.89 ms per 32 queries).  KS = 4 rings fit two.
-__global__ __launch_bounds__(kBlock, QB == 1 || (NS == 2 && KS == 2) ? 4 : (NS ? 2 : 3)) void sq8_mfma(Sq8Params p) {
+__global__ __launch_bounds__(kBlock, QB == 1 || (NS == 2 && KS == 2) ? 4 : (NS ? 2 : 3)) void sq8_mfma(Sq8MfmaParams p) {
     constexpr bool RING = NS > 0;
     // insertions bounded one pair per lane (see the insertion loop) — not in the 4-workgroup KS = 2, 2-slot ring
     // instances capped at 128 VGPRs (nor KS = 16, QB = 1), where its extra live values spilled inside the loop
@@ -1196,7 +1196,7 @@ __global__ __launch_bounds__(kBlock, QB == 1 || (NS == 2 && KS == 2) ? 4 : (NS ?
     }
 }
 
-using Sq8MfmaFn = void (*)(Sq8Params);
+using Sq8MfmaFn = void (*)(Sq8MfmaParams);
 static const int kMfmaKS[6] = {2, 4, 6, 8, 12, 16};
 #define OSK_MFMA_SIMS(KS, QB, RG) {sq8_mfma<KS, QB, RG, 0>, sq8_mfma<KS, QB, RG, 1>, sq8_mfma<KS, QB, RG, 2>, \
                                    sq8_mfma<KS, QB, RG, 3>}
@@ -1265,7 +1265,7 @@ hipError_t launch_sq8_tile(const void* q8, int64_t n_rows, int u8, int ks, void*
     return hipGetLastError();
 }
 
-hipError_t launch_sq8_mfma(const Sq8Params& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+hipError_t launch_sq8_mfma(const Sq8MfmaParams& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     int c = 0;
     while (c < 5 && 4 * kMfmaKS[c] < p.units8) ++c;
     if (4 * kMfmaKS[c] < p.units8) return hipErrorInvalidValue;
@@ -1402,10 +1402,10 @@ __global__ __launch_bounds__(kSettleThreads) void sq8_settle(SettleParams p) {
     if (p.trace && tid == 0) p.trace[((size_t)q * p.n_slices + g) * 8 + 2] = wall_clock64();
     if (tid == 0) {
         if (exact) {
-            if ((atomicOr(&p.flags[q], 1) & 1) == 0) atomicAdd(&p.counters[0], 1ull);
-            atomicAdd(&p.counters[2], (unsigned long long)__popc(exact));
+            if ((atomicOr(&p.flags[q], 1) & 1) == 0) atomicAdd(&p.counters[kCtrFallbackQueries], 1ull);
+            atomicAdd(&p.counters[kCtrExactLists], (unsigned long long)__popc(exact));
         }
-        if (nc) atomicAdd(&p.counters[1], (unsigned long long)nc);
+        if (nc) atomicAdd(&p.counters[kCtrRescoredRows], (unsigned long long)nc);
     }
 
     // (c) exact re-score of the candidates
@@ -1428,14 +1428,14 @@ __global__ __launch_bounds__(kSettleThreads) void sq8_settle(SettleParams p) {
     if (p.trace && tid == 0) p.trace[((size_t)q * p.n_slices + g) * 8 + 3] = wall_clock64();
     // (c') overflowed lists: every accepted row of the scan wave's range (the scan's split of its
     // tile: per_wave = ⌈rows / 4R_s⌉·R_s), walked by this block's 4 waves (filter pushdown included)
-    for (uint32_t bits = exact; bits && p.gtiles; bits &= bits - 1u) {
+    for (uint32_t bits = exact; bits && p.gather.gtiles; bits &= bits - 1u) {
         // gather mode: the scan wave's quarter of its gather tile's compacted ordinals (all accepted)
         const int list = sl.x + __builtin_ctz(bits);
-        const int4 gt = p.gtiles[list >> 2];
+        const int4 gt = p.gather.gtiles[list >> 2];
         const SegDev seg = p.segs[gt.x];
         int64_t lb0, lb1;
-        gather_wave_range(min<int64_t>(p.scnt[gt.x], seg.n_rows), gt.z, gt.w, p.gather_min, list & 3, lb0, lb1);
-        const uint32_t* __restrict__ C = p.comp + p.seg_vrow[gt.x];
+        gather_wave_range(min<int64_t>(p.gather.scnt[gt.x], seg.n_rows), gt.z, gt.w, p.gather.gather_min, list & 3, lb0, lb1);
+        const uint32_t* __restrict__ C = p.gather.comp + p.seg_vrow[gt.x];
         const int64_t per_wave = ((lb1 - lb0 + kSettleWaves * R - 1) / (kSettleWaves * R)) * R;
         const int64_t wb = lb0 + wave * per_wave;
         const int64_t we = min(wb + per_wave, lb1);
@@ -1449,7 +1449,7 @@ __global__ __launch_bounds__(kSettleThreads) void sq8_settle(SettleParams p) {
             wave_offer(valid ? make_key(sc, (uint32_t)(seg.doc_base + doc)) : 0ull, t == 0, lk, thr, lane, k);
         }
     }
-    for (uint32_t bits = p.gtiles ? 0u : exact; bits; bits &= bits - 1u) {
+    for (uint32_t bits = p.gather.gtiles ? 0u : exact; bits; bits &= bits - 1u) {
         const int list = sl.x + __builtin_ctz(bits);
         const TileDev td = p.tiles[list >> 2];
         const SegDev seg = p.segs[td.seg];
@@ -1734,10 +1734,10 @@ __global__ __launch_bounds__(kWideSettleThreads) void sq8_settle_wide(SettlePara
     }
     if (tid == 0) {
         if (n_exact) {
-            if ((atomicOr(&p.flags[q], 1) & 1) == 0) atomicAdd(&p.counters[0], 1ull);
-            atomicAdd(&p.counters[2], n_exact);
+            if ((atomicOr(&p.flags[q], 1) & 1) == 0) atomicAdd(&p.counters[kCtrFallbackQueries], 1ull);
+            atomicAdd(&p.counters[kCtrExactLists], n_exact);
         }
-        if (n_res) atomicAdd(&p.counters[1], n_res);
+        if (n_res) atomicAdd(&p.counters[kCtrRescoredRows], n_res);
     }
     // (c) the shard's top k
     s_lists[wave * 64 + lane] = lane < k ? lk : 0ull;
@@ -1767,7 +1767,7 @@ static const SettleFn kSettleWide[6][2] = {OSK_SETTLE_WIDE_ROW(4, 2),  OSK_SETTL
                                            OSK_SETTLE_WIDE_ROW(16, 8), OSK_SETTLE_WIDE_ROW(16, 12)};
 
 hipError_t launch_sq8_settle_wide(int cfg, int nq, const SettleParams& p, hipStream_t s) {
-    if (p.accept || p.gtiles || !p.shard_tile_begin || p.k < 1 || p.k > 64 || cfg < 0 || cfg > 5) return hipErrorInvalidValue;
+    if (p.accept || p.gather.gtiles || !p.shard_tile_begin || p.k < 1 || p.k > 64 || cfg < 0 || cfg > 5) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kSettleWide[cfg][p.sim == SIM_EUCLIDEAN ? 1 : 0], dim3(p.n_shards, nq), dim3(kWideSettleThreads), 0,
                        s, p);
     return hipGetLastError();

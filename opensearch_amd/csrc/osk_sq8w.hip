@@ -393,7 +393,7 @@ struct WideGeom {
 // are set up once per launch.  8 waves, two per SIMD; every wave scores its 32 queries against every group
 // of a step.  Each wave flushes its queries' lists when its quarter ends.
 template <int KS, int SIM>
-__global__ __launch_bounds__(kWideThreads, 1) void sq8_wide(Sq8Params p) {
+__global__ __launch_bounds__(kWideThreads, 1) void sq8_wide(Sq8WideParams p) {
     typedef int i32x4 __attribute__((ext_vector_type(4)));
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     using Geo = WideGeom<KS>;
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(kWideThreads, 1) void sq8_wide(Sq8Params p) {
     for (int i = tid; i < n_mine; i += kWideThreads) {
         const int j = qbeg + (int)blockIdx.x + i * G;
         WideQuarter d = p.wide_qtable ? static_cast<const WideQuarter*>(p.wide_qtable)[j]
-                                      : wide_quarter_of(p.tiles, p.tile_order, j, KS, p.rows8t, p.auxt, p.seg_vrow,
+                                      : wide_quarter_of(p.wtiles, p.tile_order, j, KS, p.rows8w, p.auxt, p.seg_vrow,
                                                         p.quarter_bm);
         if (pilot) d.nrows = min(d.nrows, p.pilot_rows > 0 ? p.pilot_rows : kWidePilotRows);   // its first rows
         s_quart[i] = d;
@@ -1232,14 +1232,14 @@ __global__ __launch_bounds__(kWideThreads, 1) void sq8_wide(Sq8Params p) {
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) n_pairs += __shfl_xor(n_pairs, o);
         if (lane == 0) {
-            atomicAdd(&p.counters[4], (unsigned long long)n_events);
-            atomicAdd(&p.counters[5], (unsigned long long)n_pairs);
-            atomicAdd(&p.counters[7], (unsigned long long)n_slow);
+            atomicAdd(&p.counters[kCtrWideEvents], (unsigned long long)n_events);
+            atomicAdd(&p.counters[kCtrWidePairs], (unsigned long long)n_pairs);
+            atomicAdd(&p.counters[kCtrWideSlowSteps], (unsigned long long)n_slow);
             if (wave == 0) {
-                atomicAdd(&p.counters[6], (unsigned long long)cyc_wait);
-                atomicAdd(&p.counters[8], (unsigned long long)cyc_loop);
-                atomicAdd(&p.counters[9], (unsigned long long)cyc_slow);
-                atomicAdd(&p.counters[10], (unsigned long long)cyc_drain);
+                atomicAdd(&p.counters[kCtrWideWaitCycles], (unsigned long long)cyc_wait);
+                atomicAdd(&p.counters[kCtrWideLoopCycles], (unsigned long long)cyc_loop);
+                atomicAdd(&p.counters[kCtrWideSlowCycles], (unsigned long long)cyc_slow);
+                atomicAdd(&p.counters[kCtrWideDrainCycles], (unsigned long long)cyc_drain);
             }
         }
     }
@@ -1283,7 +1283,7 @@ __device__ __forceinline__ const char* rfl_ptr_c(const void* ptr) {
 }
 
 template <int SIM, bool PILOT>
-__global__ __launch_bounds__(kWideThreads, 1) void sq8_wide_rows(Sq8Params p) {
+__global__ __launch_bounds__(kWideThreads, 1) void sq8_wide_rows(Sq8WideParams p) {
     typedef int i32x4 __attribute__((ext_vector_type(4)));
     constexpr int NQB = kWideQ / 16, NR = kRowsNR, PB = kRowsQB;
     static_assert(PB == 2 || PB == 4, "passes of 2 or 4 query blocks");
@@ -1354,7 +1354,7 @@ __global__ __launch_bounds__(kWideThreads, 1) void sq8_wide_rows(Sq8Params p) {
     for (int i = tid; i < n_mine; i += kWideThreads) {
         const int j = qbeg + (int)blockIdx.x + i * G;
         WideQuarter d = p.wide_qtable ? static_cast<const WideQuarter*>(p.wide_qtable)[j]
-                                      : wide_quarter_of(p.tiles, p.tile_order, j, 2, p.rows8t, p.auxt, p.seg_vrow,
+                                      : wide_quarter_of(p.wtiles, p.tile_order, j, 2, p.rows8w, p.auxt, p.seg_vrow,
                                                         p.quarter_bm);
         if (PILOT) d.nrows = min(d.nrows, p.pilot_rows > 0 ? p.pilot_rows : kWidePilotRows);   // (its first rows)
         s_quart[i] = d;
@@ -1945,26 +1945,26 @@ __global__ __launch_bounds__(kWideThreads, 1) void sq8_wide_rows(Sq8Params p) {
 #ifdef OSK_TESTING
     cyc_qend += clock64() - t_e0;
     if (!PILOT && p.counters && tid == 0) {
-        atomicAdd(&p.counters[16], (unsigned long long)(clock64() - t_start));
-        atomicAdd(&p.counters[17], (unsigned long long)cyc_setup);
-        atomicAdd(&p.counters[18], (unsigned long long)cyc_qend);
-        atomicAdd(&p.counters[19], (unsigned long long)cyc_first);
-        atomicAdd(&p.counters[20], (unsigned long long)(t_bar - t_start));   // setup: to the first barrier
-        atomicAdd(&p.counters[21], (unsigned long long)(t_frag - t_bar));    // then the fragments' arrival
+        atomicAdd(&p.counters[kCtrRowsTotalCycles], (unsigned long long)(clock64() - t_start));
+        atomicAdd(&p.counters[kCtrRowsSetupCycles], (unsigned long long)cyc_setup);
+        atomicAdd(&p.counters[kCtrRowsQuarterEndCycles], (unsigned long long)cyc_qend);
+        atomicAdd(&p.counters[kCtrRowsFirstWaitCycles], (unsigned long long)cyc_first);
+        atomicAdd(&p.counters[kCtrRowsSetupBarrierCycles], (unsigned long long)(t_bar - t_start));   // setup: to the first barrier
+        atomicAdd(&p.counters[kCtrRowsSetupFragmentCycles], (unsigned long long)(t_frag - t_bar));    // then the fragments' arrival
     }
     if (p.counters) {
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) n_pairs += __shfl_xor(n_pairs, o);
         if (lane == 0) {
-            atomicAdd(&p.counters[4], (unsigned long long)n_events);
-            atomicAdd(&p.counters[5], (unsigned long long)n_pairs);
-            atomicAdd(&p.counters[7], (unsigned long long)n_slow);
+            atomicAdd(&p.counters[kCtrWideEvents], (unsigned long long)n_events);
+            atomicAdd(&p.counters[kCtrWidePairs], (unsigned long long)n_pairs);
+            atomicAdd(&p.counters[kCtrWideSlowSteps], (unsigned long long)n_slow);
         }
     }
 #endif
 }
 
-using WideFn = void (*)(Sq8Params);
+using WideFn = void (*)(Sq8WideParams);
 #define OSK_WIDE_SIMS(KS) {sq8_wide<KS, 0>, sq8_wide<KS, 1>, sq8_wide<KS, 2>, sq8_wide<KS, 3>}
 static const WideFn kWide[4][4] = {OSK_WIDE_SIMS(2), OSK_WIDE_SIMS(4), OSK_WIDE_SIMS(8), OSK_WIDE_SIMS(12)};
 static_assert(sizeof(WideCold) <= 128, "WideCold: 128 B of static LDS reserved");
@@ -1981,7 +1981,7 @@ static size_t sq8_wide_lds(int ks, int sim, int n_shards, int n_mine) {
            (n_shards <= kWideMaxFloorShards ? (size_t)n_shards * kWideQ * 4 : 0) + (size_t)n_mine * sizeof(WideQuarter);
 }
 
-using RowsFn = void (*)(Sq8Params);
+using RowsFn = void (*)(Sq8WideParams);
 static const RowsFn kWideRows[2][4] = {{sq8_wide_rows<0, false>, sq8_wide_rows<1, false>, sq8_wide_rows<2, false>,
                                         sq8_wide_rows<3, false>},
                                        {sq8_wide_rows<0, true>, sq8_wide_rows<1, true>, sq8_wide_rows<2, true>,
@@ -2010,9 +2010,9 @@ static_assert(kWideWaves * kRowsNR * kRowsSlot >= kWideQ * kKQ * 12, "the lists 
 static constexpr int kRowsMinQcap = 128;   // deferred entries per owner wave at least (else more workgroups)
 bool sq8_wide_rows_supported(int u8) { return sq8_wide_supported(u8) && sq8_wide_ks(u8) == 2; }
 
-hipError_t launch_sq8_wide_rows(const Sq8Params& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (!sq8_wide_rows_supported(p.units8) || p.q_count < 1 || p.q_count > kWideQ || p.accept || p.gtiles ||
-        p.sim < 0 || p.sim > 3 || !p.rows8t || !p.auxt || p.n_lists != 4 * p.n_tiles || p.k < 1 || p.k > kKQ ||
+hipError_t launch_sq8_wide_rows(const Sq8WideParams& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    if (!sq8_wide_rows_supported(p.units8) || p.q_count < 1 || p.q_count > kWideQ || p.accept ||
+        p.sim < 0 || p.sim > 3 || !p.rows8w || !p.auxt || p.n_lists != 4 * p.n_tiles || p.k < 1 || p.k > kKQ ||
         p.n_shards < 1 || p.wide_grid < 1 || (p.pilot && !p.pilot_keys) || (!p.pilot && !p.quarter_bm))
         return hipErrorInvalidValue;
     const int nq4 = (p.quarter_end > 0 ? p.quarter_end : 4 * p.n_tiles) - p.quarter_begin;
@@ -2026,7 +2026,7 @@ hipError_t launch_sq8_wide_rows(const Sq8Params& p, hipStream_t s, hipEvent_t ev
         grid *= 2;
     size_t lds = sq8_wide_rows_lds(p.n_shards, (nq4 + grid - 1) / grid);
     // the queues: what LDS leaves, ≤ 1024 entries per owner wave (multiples of 64); tests ask for fewer
-    Sq8Params q = p;
+    Sq8WideParams q = p;
     const int room = (int)std::min<size_t>(1024, (cap - lds) / (kWideWaves * sizeof(uint2)) / 64 * 64);
     q.wide_qcap = p.wide_qcap > 0 ? std::min(p.wide_qcap, room) : room;
     lds += (size_t)kWideWaves * q.wide_qcap * sizeof(uint2);
@@ -2038,9 +2038,9 @@ hipError_t launch_sq8_wide_rows(const Sq8Params& p, hipStream_t s, hipEvent_t ev
     return hipGetLastError();
 }
 
-hipError_t launch_sq8_wide(const Sq8Params& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (!sq8_wide_supported(p.units8) || p.q_count < 1 || p.q_count > kWideQ || p.accept || p.gtiles ||
-        p.sim < 0 || p.sim > 3 || !p.rows8t || !p.auxt || p.n_lists != 4 * p.n_tiles || p.k < 1 || p.k > kKQ ||
+hipError_t launch_sq8_wide(const Sq8WideParams& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    if (!sq8_wide_supported(p.units8) || p.q_count < 1 || p.q_count > kWideQ || p.accept ||
+        p.sim < 0 || p.sim > 3 || !p.rows8w || !p.auxt || p.n_lists != 4 * p.n_tiles || p.k < 1 || p.k > kKQ ||
         p.n_shards < 1 || p.wide_grid < 1 || (p.pilot && !p.pilot_keys) || (!p.pilot && !p.quarter_bm))
         return hipErrorInvalidValue;
     const int ks = sq8_wide_ks(p.units8);
@@ -2055,7 +2055,7 @@ hipError_t launch_sq8_wide(const Sq8Params& p, hipStream_t s, hipEvent_t ev_star
     size_t lds = sq8_wide_lds(ks, p.sim, p.n_shards, (nq4 + grid - 1) / grid);
     // the deferred-insertion queues in what LDS is left: ≥ 256 entries per wave (one (group, query block) adds at
     // most 64 lanes × 4 rows), else the immediate insertions (and always for the pilot)
-    Sq8Params q = p;
+    Sq8WideParams q = p;
     const int room = (int)((lcap - lds) / (kWideWaves * sizeof(uint2))) / 64 * 64;
     q.wide_qcap = (!p.pilot && p.wide_defer && room >= 256) ? std::min(room, 512) : 0;
     lds += (size_t)kWideWaves * q.wide_qcap * sizeof(uint2);

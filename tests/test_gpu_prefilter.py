@@ -284,3 +284,38 @@ def test_mfma_ring_depths(slots, dim, sim, scan_kernel):
         for r in readers:
             r.close()
         sparse.close()
+
+
+COUNTER_NAMES = [
+    "mfma_calls", "mfma_fallback_queries", "sq8_calls", "sq6_calls", "select_calls", "sq8_wide_calls",
+    "threshold_calls", "threshold_sq8_calls", "nested_calls",
+    "host_slots", "host_batches", "host_batched_requests", "sq8_slices", "mfma_full_tiles",
+    "sq8_fallback_queries", "sq8_rescored_rows", "sq8_exact_tiles",
+    "sq6_rebound_rows", "sq6_rebound_gathered_rows", "sq6_rebound_passes", "sq6_rebound_max_wg_cycles",
+    "sq8_wide_events", "sq8_wide_pairs", "sq8_wide_wait_cycles", "sq8_wide_slow_steps",
+    "sq8_wide_loop_cycles", "sq8_wide_slow_cycles", "sq8_wide_drain_cycles",
+    "sq8_rows_total_cycles", "sq8_rows_setup_cycles", "sq8_rows_quarter_end_cycles", "sq8_rows_first_wait_cycles",
+    "sq8_rows_setup_barrier_cycles", "sq8_rows_setup_fragment_cycles",
+    "threshold_sq8_settled_rows",
+]
+
+
+def test_every_counter_name_resolves():
+    """Every public counter name reads (a value ≥ 0), an invented one is OSK_ERR_INVALID — never another
+    counter's value — and one prefiltered search of a one-tile view moves sq8_calls and sq8_rescored_rows.
+    The testing build: the cycle counters exist only there."""
+    sim = LU.VectorSimilarityFunction.DOT_PRODUCT
+    rows = corpus(256, 16, sim, 31)
+    with _lib.testing():
+        ds, readers = view_of([rows], sim)
+        try:
+            ds.search(corpus(1, 16, sim, 32), 4, 0, 4)
+            for name in COUNTER_NAMES:
+                assert ds.counter(name) >= 0, name
+            with pytest.raises(_lib.OskError) as err:
+                ds.counter("sq8_no_such_counter")
+            assert err.value.code == _lib.OSK_ERR_INVALID
+            assert ds.counter("sq8_calls") == 1
+            assert ds.counter("sq8_rescored_rows") >= 4
+        finally:
+            close_all(ds, readers)
