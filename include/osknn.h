@@ -254,6 +254,13 @@ int32_t osk_view_scan_time(osk_view* view, double* total_ms, int64_t* calls);
  *                     one (dims ≥ 512; default 1) instead of the int8 copy...
  *   "sq6_probe_pct"   ...unless the view's first 4 such calls re-bound more than this % of the rows from
  *                     the int8 copy (default 10; the view then keeps the int8 tier)
+ *   "sq6_share"       0|1 single queries in flight on several views over one segment set (equal tile
+ *                     tables: a searcher's per-thread views, a view's leased replicas) share 6-bit corpus
+ *                     passes: each view posts its query and a pass scores every posted query against one
+ *                     read of a tile (default 1; 0 = every call its own pass; results are bit-identical
+ *                     either way).  "sq6_share_idle" 0|1: a pass whose own tiles are all
+ *                     done still scans for the others (default 0); "sq6_share_min_tiles": views of fewer
+ *                     tiles do not share (default 0 = views of one round of resident workgroups or less)
  *   "sq8_mfma_min"    prefilter batches of at least this many queries scan on int8 MFMA (sq8_mfma,
  *                     default 2; 0 = always the VALU sq8_scan)
  *   "sq8_mfma_queries"  16 | 32 queries per sq8_mfma launch (default 32)
@@ -291,7 +298,8 @@ int32_t osk_view_scan_time(osk_view* view, double* total_ms, int64_t* calls);
  * The testing build (libosknn_testing.so) also accepts "sq8_mfma_ablate", "mfma_ablate" (A/B timing,
  * results wrong), "sq8_force_fallback" (every prefilter list re-scanned exactly), "settle_trace" and
  * "thr_sq8_all_maybe" (the int8 first pass of a threshold search decides nothing: every accepted candidate
- * row is re-scored exactly; results unchanged); the shipped library returns OSK_ERR_UNSUPPORTED for them. */
+ * row is re-scored exactly; results unchanged) and "sq6_share_limit" (a shared 6-bit pass serves other views
+ * only in its first N workgroups); the shipped library returns OSK_ERR_UNSUPPORTED for them. */
 int32_t osk_tune_set(const char* key, int64_t value);
 
 /* Batched-path counters of a view: searches that took the MFMA path, and queries among them whose
@@ -300,6 +308,9 @@ int32_t osk_view_stats(osk_view* view, int64_t* batched_calls, int64_t* fallback
 /* Named counters of a view: "mfma_calls", "mfma_fallback_queries" (as osk_view_stats),
  * "sq8_calls" (prefiltered searches), "sq6_calls" (those whose scan read the 6-bit tier),
  * "sq6_rebound_rows" (rows the 6-bit scan re-bounded from the int8 copy, all calls),
+ * "sq6_tiles_own" (tiles the view's shared passes scanned for its own query), "sq6_tiles_by_others" (tiles of
+ * its queries that another view's pass had scanned), "sq6_tiles_helped" ((query, tile) pairs its passes
+ * scanned for other views), "scan_tiles" (the view's scan tiles), "seg_refs" (references on its segments),
  * "sq8_fallback_queries" (queries where some tile's candidate
  * list overflowed past the certificate and the tile was re-scanned exactly), "sq8_exact_tiles"
  * (such tiles), "sq8_rescored_rows" (rows re-scored exactly, all calls), "select_calls" (searches

@@ -147,6 +147,7 @@ std::vector<SegDev> seg_devs(const osk_view* v) {
 
 namespace {
 void sq6_forget_segment(const osk_seg* sg);   // (below, with the 6-bit tier's in-flight records)
+void sq6_share_detach(osk_view* v);           // (below, with the share groups)
 }
 
 osk_seg::~osk_seg() {
@@ -194,6 +195,7 @@ int64_t osk_seg::hbm_bytes() const {
 
 osk_view::~osk_view() {
     for (osk_view* r : replicas) delete r;   // (no lease is live: the caller's release contract)
+    sq6_share_detach(this);   // (waits for the group's scans: they may be writing this view's lists)
     for (hipStream_t st : lease_streams)
         if (st) (void)hipStreamDestroy(st);
     if (xs_event) (void)hipEventDestroy(xs_event);
@@ -343,6 +345,10 @@ int32_t osk_tune_set(const char* key, int64_t value) {
         {"sq6_rebound_stride", &g_tuning.sq6_rebound_stride, 0, 1, false},
         {"sq6_rebound_retest", &g_tuning.sq6_rebound_retest, 0, 1, false},
         {"sq6_rebound_wgs", &g_tuning.sq6_rebound_wgs, 0, 16, false},
+        {"sq6_share", &g_tuning.sq6_share, 0, 1, false},
+        {"sq6_share_min_tiles", &g_tuning.sq6_share_min_tiles, 0, 1 << 24, false},
+        {"sq6_share_idle", &g_tuning.sq6_share_idle, 0, 1, false},
+        {"sq6_share_limit", &g_tuning.sq6_share_limit, -1, 1 << 24, true},
         {"sq8_mfma_ring", &g_tuning.sq8_mfma_ring, -1, 8, false},
         {"i8_stream", &g_tuning.i8_stream, 0, 1, false},
         {"call_timing", &g_tuning.call_timing, 0, 1, false},
@@ -752,6 +758,7 @@ int32_t osk_view_create(osk_seg* const* segs, int32_t n_segs, const int32_t* seg
     }
     v->shard_tile_begin[n_shards] = (int32_t)tiles.size();
     v->n_tiles = (int)tiles.size();
+    v->h_tiles = tiles;
     for (const TileDev& td : tiles) v->max_tile_rows = std::max(v->max_tile_rows, td.row_end - td.row_begin);
     // each tile's first row's slot in its shard's candidate region (the select path's collect)
     std::vector<int32_t> tile_coff(std::max<size_t>(1, tiles.size()), 0);
@@ -776,6 +783,7 @@ int32_t osk_view_create(osk_seg* const* segs, int32_t n_segs, const int32_t* seg
         std::stable_sort(key.begin(), key.end(), [](auto& a, auto& b) { return a.first < b.first; });
         for (size_t i = 0; i < key.size(); ++i) tile_order[i] = key[i].second;
     }
+    v->h_tile_order = tile_order;
 
     v->seg_doc_base.resize(n_segs);
     for (int i = 0; i < n_segs; ++i) v->seg_doc_base[i] = seg_doc_base ? seg_doc_base[i] : 0;
@@ -1705,6 +1713,122 @@ int sq8_wide_first_pass(int nql, int wgrid) {
     return phase > 1 ? std::min(nql / 2, rounds * wgrid) : 0;
 }
 
+// ---- Share groups of the 6-bit tier: views over one segment set with equal tile tables (a
+// searcher's add_view views, a view's leased replicas) whose single queries in flight are served by shared
+// corpus passes (osk_sq6.hip sq6_scan_shared).  A group is a ref-counted registry entry keyed by the device,
+// the ordered segment list, the tile table and its dispatch order; it owns kShareSlots slots on the device (the
+// posted queries) and a word per (slot, tile) carrying the generation whose tile is done.  Its scans are
+// chained: each waits, on its own stream, for the event of the one enqueued before it (the group mutex covers
+// wait, launch and record), so no scan sees another's tile half done and nothing is cleared per call. ----
+// The registry's key: two views share only if all of this compares equal.
+struct Sq6ShareKey {
+    int device = 0, n_shards = 0, dim = 0, sim = 0;
+    std::vector<const osk_seg*> segs;
+    std::vector<TileDev> tiles;
+    std::vector<int32_t> order;
+    bool operator==(const Sq6ShareKey& o) const {
+        if (device != o.device || n_shards != o.n_shards || dim != o.dim || sim != o.sim || segs != o.segs ||
+            order != o.order || tiles.size() != o.tiles.size())
+            return false;
+        for (size_t i = 0; i < tiles.size(); ++i)
+            if (tiles[i].seg != o.tiles[i].seg || tiles[i].shard != o.tiles[i].shard ||
+                tiles[i].row_begin != o.tiles[i].row_begin || tiles[i].row_end != o.tiles[i].row_end)
+                return false;
+        return true;
+    }
+};
+struct Sq6Group {
+    Sq6ShareKey key;
+    std::mutex mu;                       // slots, generations, the event chain
+    int attached = 0;
+    bool used[kShareSlots] = {};
+    uint32_t gen[kShareSlots] = {};      // the last generation each slot posted (kept across owners: a word of an
+    unsigned long long seq = 0;          // earlier owner never equals a later generation)
+    hipEvent_t last = nullptr;           // the last shared scan enqueued
+    bool has_last = false;
+    Sq6Slot* d_slots = nullptr;
+    uint32_t* d_done = nullptr;          // [kShareSlots][n_tiles]
+};
+std::mutex g_sq6_groups_mu;              // the registry (outer to a group's mu)
+std::vector<Sq6Group*> g_sq6_groups;
+
+// Join the view's group (created on first use) and take a slot; a view that finds none does not share
+// (caller holds v->mu; the view's device is current).
+int32_t sq6_share_attach(osk_view* v) {
+    Sq6ShareKey key{v->device, v->n_shards, v->dim, v->sim, {v->segs.begin(), v->segs.end()}, v->h_tiles, v->h_tile_order};
+    std::lock_guard<std::mutex> reg(g_sq6_groups_mu);
+    Sq6Group* grp = nullptr;
+    for (Sq6Group* c : g_sq6_groups)
+        if (c->key == key) grp = c;
+    if (!grp) {
+        auto fresh = std::make_unique<Sq6Group>();
+        fresh->key = std::move(key);
+        const size_t words = (size_t)kShareSlots * std::max(1, v->n_tiles);
+        OSK_HIP(hipMalloc(&fresh->d_slots, sizeof(Sq6Slot) * kShareSlots));
+        hipError_t e = hipMalloc(&fresh->d_done, sizeof(uint32_t) * words);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&fresh->last, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipMemset(fresh->d_slots, 0, sizeof(Sq6Slot) * kShareSlots);
+        if (e == hipSuccess) e = hipMemset(fresh->d_done, 0, sizeof(uint32_t) * words);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (the fills land before any stream posts)
+        if (e != hipSuccess) {
+            (void)hipFree(fresh->d_slots);
+            if (fresh->d_done) (void)hipFree(fresh->d_done);
+            if (fresh->last) (void)hipEventDestroy(fresh->last);
+            OSK_HIP(e);
+        }
+        grp = fresh.release();
+        g_sq6_groups.push_back(grp);
+    }
+    std::lock_guard<std::mutex> lk(grp->mu);
+    for (int s = 0; s < kShareSlots; ++s)
+        if (!grp->used[s]) {
+            grp->used[s] = true;
+            grp->attached += 1;
+            v->share_group = grp;
+            v->share_slot = s;
+            break;
+        }
+    v->share_tried = true;   // (a failed allocation above leaves the view free to try again)
+    return OSK_OK;
+}
+
+// Leave the group: after its last scan has completed (a scan may be writing this view's lists or reading its
+// posted query), the slot's generation word is cleared so no later scan reads the descriptor; the group goes
+// with its last view.
+void sq6_share_detach(osk_view* v) {
+    Sq6Group* grp = static_cast<Sq6Group*>(v->share_group);
+    if (!grp) return;
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(grp->key.device);
+    {
+        // the group lock keeps later scans out while the last one drains and the slot is cleared; the registry
+        // lock is not held over the wait, so other groups attach and detach meanwhile (the group itself stays:
+        // this view is still attached)
+        std::lock_guard<std::mutex> lk(grp->mu);
+        if (grp->has_last) (void)hipEventSynchronize(grp->last);
+        (void)hipMemset(&grp->d_slots[v->share_slot].gen, 0, sizeof(uint32_t));
+        (void)hipStreamSynchronize(nullptr);
+    }
+    bool last_view = false;
+    {
+        std::lock_guard<std::mutex> reg(g_sq6_groups_mu);
+        std::lock_guard<std::mutex> lk(grp->mu);
+        grp->used[v->share_slot] = false;
+        last_view = --grp->attached == 0;
+        if (last_view) g_sq6_groups.erase(std::remove(g_sq6_groups.begin(), g_sq6_groups.end(), grp), g_sq6_groups.end());
+    }
+    v->share_group = nullptr;
+    v->share_slot = -1;
+    if (last_view) {   // (off the registry: no view can find it any more)
+        (void)hipFree(grp->d_slots);
+        (void)hipFree(grp->d_done);
+        (void)hipEventDestroy(grp->last);
+        delete grp;
+    }
+    if (cur >= 0) (void)hipSetDevice(cur);
+}
+
 // ---- Certified int8 prefilter search (float32, k ≤ kKQ): int8 scan → settle per slice of tiles (exact
 // re-score of the rows the certificate cannot exclude; a tile whose list overflowed is re-scanned
 // exactly inside the settle) → per-shard merge.  Nothing waits on the host.  sq8_search decides on one of
@@ -1716,6 +1840,7 @@ struct Sq8Plan {
     bool gather;    // kValu: a filtered scan over the compacted accepted ordinals
     bool probing;   // kSq6: some segment is still calibrating the tier (it may yet turn it off)
     bool probe6;    // kSq6: this call counts its int8 re-bounds per segment (one probe in flight per view)
+    bool share;     // kSq6: the view's share group has another view: post the query and take the shared pass
 };
 // one search call's arguments
 struct Sq8Call {
@@ -1749,7 +1874,7 @@ struct Sq8Lists {
 // hipFreeAsync behind the events of the launches still reading it: no device wait).
 Sq8Plan sq8_decide(const osk_view* v, int nq, bool filtered, bool wide_pick,
                    std::shared_lock<std::shared_mutex>& tier_lock) {
-    Sq8Plan plan{Sq8Strategy::kValu, false, false, false};
+    Sq8Plan plan{Sq8Strategy::kValu, false, false, false, false};
     if (g_tuning.sq8_mfma_min > 0 && nq >= g_tuning.sq8_mfma_min && sq8_mfma_supported(v->units8)) {
         plan.strategy = !g_tuning.sq8_force_fallback && wide_pick ? Sq8Strategy::kWide : Sq8Strategy::kMfma;
         return plan;
@@ -1987,10 +2112,11 @@ int32_t scan_wide(const Sq8Call& c, Sq8Lists& out) {
 }
 
 // The 6-bit tier, one query: pilot → streaming pass over the 6-bit codes → int8 re-bound of the rows that
-// passed (launch_sq6_scan); sq6_prep reserved and the fused prep filled its query form.
-int32_t scan_sq6(const Sq8Call& c, const Sq8Plan& plan, Sq8Lists& out) {
+// passed; sq6_prep reserved and the fused prep filled its query form.  A call whose view is in a share group
+// with another view (plan.share) posts its query after the pilot and takes the group's shared pass, chained
+// behind the group's previous one; every other call launches today's three kernels (launch_sq6_scan).
+int32_t sq6_params(const Sq8Call& c, const Sq8Plan& plan, Sq6Params& p, Sq8Lists& out) {
     osk_view* v = c.v;
-    Sq6Params p{};
     int32_t rc = sq8_lists(c, v->n_tiles, kSq6ScanR, p, out);
     if (rc) return rc;
     OSK_HIP(v->ws_cand6.reserve(sizeof(uint2) * (size_t)p.n_lists * kSq6Cap));
@@ -2011,6 +2137,72 @@ int32_t scan_sq6(const Sq8Call& c, const Sq8Plan& plan, Sq8Lists& out) {
     p.cap6 = kSq6Cap;
     p.seg_rebound = plan.probe6 ? v->d_seg_rebound.as<unsigned long long>() : nullptr;
     sq8_chunk(v, p, 0, 1, c.nq);
+    return OSK_OK;
+}
+
+// Steps 1 and 2 of a sharing call: the pilot, then the post of the view's slot with the group's next generation
+int32_t sq6_share_post(const Sq8Call& c, Sq6Params& p) {
+    osk_view* v = c.v;
+    Sq6Group* grp = static_cast<Sq6Group*>(v->share_group);
+    OSK_HIP(launch_sq6_pilot(p, v->dim, c.st));
+    Sq6Slot d{};
+    {
+        std::lock_guard<std::mutex> lk(grp->mu);
+        uint32_t& g = grp->gen[v->share_slot];
+        g = g + 1u ? g + 1u : 1u;   // (never 0: an empty slot)
+        d.gen = g;
+        d.seq = ++grp->seq;
+    }
+    d.k = p.k;
+    d.q6 = p.q6;
+    d.qc6 = p.qc6;
+    d.qn_dev = p.qn_dev;
+    d.floor = p.floor;
+    d.cand6 = p.cand6;
+    d.cnt6 = p.cnt6;
+    OSK_HIP(launch_sq6_post(grp->d_slots + v->share_slot, d, c.st));
+    p.sh_slots = grp->d_slots;
+    p.sh_done = grp->d_done;
+    p.sh_slot = v->share_slot;
+    p.sh_gen = d.gen;
+    const int limit = g_tuning.sq6_share_limit;
+    p.sh_limit = limit < 0 ? INT32_MAX : limit;
+    p.sh_idle = g_tuning.sq6_share_idle;
+    return OSK_OK;
+}
+
+// Steps 3 and 4: the shared pass behind the group's previous one, then this view's own re-bound
+int32_t sq6_share_scan(const Sq8Call& c, const Sq6Params& p) {
+    osk_view* v = c.v;
+    Sq6Group* grp = static_cast<Sq6Group*>(v->share_group);
+    {
+        std::lock_guard<std::mutex> lk(grp->mu);
+        hipError_t e = grp->has_last ? hipStreamWaitEvent(c.st, grp->last, 0) : hipSuccess;
+        if (e == hipSuccess) e = launch_sq6_scan_shared(p, v->dim, c.st, launch_ev_start(v, 0), launch_ev_stop(v, 0, c.nq));
+        if (e == hipSuccess) e = hipEventRecord(grp->last, c.st);
+        if (e != hipSuccess) {
+            // the query is posted but its pass is not coming: withdraw it, behind the passes that may be reading
+            // it, so no later pass writes this view's lists while another call of the view uses them
+            if (grp->has_last) (void)hipEventSynchronize(grp->last);
+            (void)hipMemset(&grp->d_slots[v->share_slot].gen, 0, sizeof(uint32_t));
+            (void)hipStreamSynchronize(nullptr);
+            OSK_HIP(e);
+        }
+        grp->has_last = true;
+    }
+    OSK_HIP(launch_sq6_rebound(p, v->dim, c.st));
+    return OSK_OK;
+}
+
+int32_t scan_sq6(const Sq8Call& c, const Sq8Plan& plan, Sq8Lists& out) {
+    osk_view* v = c.v;
+    Sq6Params p{};
+    int32_t rc = sq6_params(c, plan, p, out);
+    if (rc) return rc;
+    if (plan.share) {
+        if ((rc = sq6_share_post(c, p)) != OSK_OK) return rc;
+        return sq6_share_scan(c, p);
+    }
     OSK_HIP(launch_sq6_scan(p, v->dim, c.st, launch_ev_start(v, 0), launch_ev_stop(v, 0, c.nq)));
     // a segment may still turn the tier off: its free waits for this launch
     return plan.probing ? sq6_track_launch(v, c.st) : OSK_OK;
@@ -2060,6 +2252,33 @@ int32_t sq8_settle_lists(const Sq8Call& c, const Sq8Lists& lists) {
     return OSK_OK;
 }
 
+// What follows a scan: the settle of its lists, the call counts, a probe call's read-back.
+int32_t sq8_finish(const Sq8Call& c, const Sq8Plan& plan, const Sq8Lists& lists) {
+    osk_view* v = c.v;
+    int32_t rc = profile_end(v, c.st, false);
+    if (rc || (rc = sq8_settle_lists(c, lists)) != OSK_OK) return rc;
+    v->sq8_calls += 1;
+    v->sq8w_calls += plan.strategy == Sq8Strategy::kWide ? 1 : 0;
+    v->sq6_calls += plan.strategy == Sq8Strategy::kSq6 ? 1 : 0;
+    if (plan.probe6) {   // read back asynchronously: a later call folds it (fold_probe), nothing waits here
+        OSK_HIP(hipMemcpyAsync(v->h_seg_rebound.p, v->d_seg_rebound.p, sizeof(unsigned long long) * v->segs.size(),
+                               hipMemcpyDeviceToHost, c.st));
+        OSK_HIP(hipEventRecord(v->ev_probe, c.st));
+        v->probe_pending = true;
+    }
+    return OSK_OK;
+}
+
+#ifdef OSK_TESTING
+// A sharing call stopped after its post (osk_testing_sq6_post), for osk_testing_sq6_resume
+struct Sq6Held {
+    Sq8Call c;
+    Sq8Plan plan;
+    Sq6Params p;
+    Sq8Lists lists;
+};
+#endif
+
 // ws_q / ws_qnorm are reserved by the caller; wide_pick: sq8_wide_pick for this call.
 int32_t sq8_search(osk_view* v, const void* d_queries, int nq, int k, int UP, const uint64_t* const* d_accept,
                    uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st,
@@ -2068,27 +2287,40 @@ int32_t sq8_search(osk_view* v, const void* d_queries, int nq, int k, int UP, co
     int32_t rc = ensure_sq8(v, st);
     if (rc || (rc = fold_probe(v, st)) != OSK_OK) return rc;
     std::shared_lock<std::shared_mutex> tier_lock(g_sq6_free_mu, std::defer_lock);
-    const Sq8Plan plan = sq8_decide(v, nq, d_accept != nullptr, wide_pick, tier_lock);
+    Sq8Plan plan = sq8_decide(v, nq, d_accept != nullptr, wide_pick, tier_lock);
+    // the 6-bit tier with every segment calibrated and kept (a kept segment never frees its copy): share the
+    // pass when another view is in the view's group (tune sq6_share, read once per call)
+    if (plan.strategy == Sq8Strategy::kSq6 && !plan.probing && g_tuning.sq6_share) {
+        if (!v->share_tried && (rc = sq6_share_attach(v)) != OSK_OK) return rc;
+        if (Sq6Group* grp = static_cast<Sq6Group*>(v->share_group)) {
+            std::lock_guard<std::mutex> lk(grp->mu);
+            // ...and the pass runs more than one round of resident workgroups: the tiles of a single round all
+            // start together, before a neighbour's post can land, so nothing would be shared and the chained
+            // passes would only lose the overlap of their tails (one shard of the headline: −7 %)
+            const int min_tiles = g_tuning.sq6_share_min_tiles;
+            const int rounds_over = view_cus(v) * std::max(1, (int)g_tuning.tile_slots_per_cu);
+            plan.share = grp->attached > 1 && v->n_tiles > (min_tiles > 0 ? min_tiles - 1 : rounds_over);
+        }
+    }
     if ((rc = sq8_prep_queries(c, d_queries, UP, plan)) != OSK_OK) return rc;
     Sq8Lists lists{};
+#ifdef OSK_TESTING
+    if (v->share_stop == 1) {
+        OSK_REQUIRE(plan.share, "the call does not share its 6-bit pass");
+        auto held = std::make_shared<Sq6Held>(Sq6Held{c, plan, Sq6Params{}, Sq8Lists{}});
+        if ((rc = sq6_params(c, plan, held->p, held->lists)) != OSK_OK || (rc = sq6_share_post(c, held->p)) != OSK_OK)
+            return rc;
+        v->share_held = held;
+        return OSK_OK;
+    }
+#endif
     switch (plan.strategy) {
         case Sq8Strategy::kValu: rc = scan_valu(c, plan.gather, lists); break;
         case Sq8Strategy::kMfma: rc = scan_mfma(c, lists); break;
         case Sq8Strategy::kWide: rc = scan_wide(c, lists); break;
         case Sq8Strategy::kSq6: rc = scan_sq6(c, plan, lists); break;
     }
-    if (rc || (rc = profile_end(v, st, false)) != OSK_OK) return rc;
-    if ((rc = sq8_settle_lists(c, lists)) != OSK_OK) return rc;
-    v->sq8_calls += 1;
-    v->sq8w_calls += plan.strategy == Sq8Strategy::kWide ? 1 : 0;
-    v->sq6_calls += plan.strategy == Sq8Strategy::kSq6 ? 1 : 0;
-    if (plan.probe6) {   // read back asynchronously: a later call folds it (fold_probe), nothing waits here
-        OSK_HIP(hipMemcpyAsync(v->h_seg_rebound.p, v->d_seg_rebound.p, sizeof(unsigned long long) * v->segs.size(),
-                               hipMemcpyDeviceToHost, st));
-        OSK_HIP(hipEventRecord(v->ev_probe, st));
-        v->probe_pending = true;
-    }
-    return OSK_OK;
+    return rc ? rc : sq8_finish(c, plan, lists);
 }
 
 // The select path (osk_select.hip): exact top-k for any k ≤ OSK_MAX_K, one query at a time.
@@ -2603,6 +2835,74 @@ int32_t osk_view_search_device(osk_view* view, const void* d_queries, int32_t n_
     OSK_GUARD_END
 }
 
+#ifdef OSK_TESTING
+// Testing build only: a sharing single-query call split at its shared pass.  osk_testing_sq6_post runs the
+// prep, the pilot and the post of the view's slot on `stream` and stops; osk_testing_sq6_resume takes up the
+// held call from the wait for the group's previous pass (the pass, the re-bound, the settle) on that stream.
+int32_t osk_testing_sq6_post(osk_view* view, const void* d_queries, int32_t k, uint64_t* d_shard_keys,
+                             int32_t* d_shard_counts, int64_t* d_visited, void* stream) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(view != nullptr, "view is null");
+    int32_t rc = check_device(view->device);
+    if (rc) return rc;
+    hipStream_t st = stream_or_default(stream, view->device);
+    std::lock_guard<std::mutex> lk(view->mu);
+    OSK_REQUIRE(!view->share_held, "a posted call of this view has not been resumed");
+    view->share_stop = 1;
+    rc = view_search_device(view, d_queries, 1, k, nullptr, d_shard_keys, d_shard_counts, d_visited, st);
+    view->share_stop = 0;
+    if (rc == OSK_OK && !view->share_held) {
+        set_error("the call did not take the 6-bit tier's shared pass");
+        return OSK_ERR_INVALID;
+    }
+    return rc;
+    OSK_GUARD_END
+}
+
+// ...and the share groups' key on the host alone: two views, each given as {device, n_shards, dim, sim}, its
+// segment handles in order, its tiles as {seg, shard, row_begin, row_end} rows and their dispatch order.
+int32_t osk_testing_sq6_share_key_equal(const int32_t* hdr_a, const uint64_t* segs_a, int32_t n_segs_a,
+                                        const int64_t* tiles_a, const int32_t* order_a, int32_t n_tiles_a,
+                                        const int32_t* hdr_b, const uint64_t* segs_b, int32_t n_segs_b,
+                                        const int64_t* tiles_b, const int32_t* order_b, int32_t n_tiles_b,
+                                        int32_t* out_equal) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(hdr_a && hdr_b && segs_a && segs_b && tiles_a && tiles_b && order_a && order_b && out_equal,
+                "null argument");
+    OSK_REQUIRE(n_segs_a >= 0 && n_segs_b >= 0 && n_tiles_a >= 0 && n_tiles_b >= 0, "negative count");
+    auto key = [](const int32_t* h, const uint64_t* sg, int ns, const int64_t* t, const int32_t* ord, int nt) {
+        Sq6ShareKey k{h[0], h[1], h[2], h[3], {}, {}, std::vector<int32_t>(ord, ord + nt)};
+        for (int i = 0; i < ns; ++i) k.segs.push_back(reinterpret_cast<const osk_seg*>((uintptr_t)sg[i]));
+        for (int i = 0; i < nt; ++i)
+            k.tiles.push_back(TileDev{(int32_t)t[4 * i], (int32_t)t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]});
+        return k;
+    };
+    *out_equal = key(hdr_a, segs_a, n_segs_a, tiles_a, order_a, n_tiles_a) ==
+                         key(hdr_b, segs_b, n_segs_b, tiles_b, order_b, n_tiles_b)
+                     ? 1
+                     : 0;
+    return OSK_OK;
+    OSK_GUARD_END
+}
+
+int32_t osk_testing_sq6_resume(osk_view* view) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(view != nullptr, "view is null");
+    int32_t rc = check_device(view->device);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(view->mu);
+    OSK_REQUIRE(view->share_held != nullptr, "no posted call to resume");
+    const std::shared_ptr<Sq6Held> held = std::static_pointer_cast<Sq6Held>(view->share_held);
+    view->share_held.reset();
+    rc = sq6_share_scan(held->c, held->p);
+    return rc ? rc : sq8_finish(held->c, held->plan, held->lists);
+    OSK_GUARD_END
+}
+#endif
+
 int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, int32_t n_queries,
                                          const float* d_min_scores, const uint64_t* const* d_accept, int32_t cap,
                                          int32_t* d_docs, float* d_scores, int32_t* d_count, int64_t* d_total,
@@ -2875,6 +3175,16 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
         *value = v->n_slices;
         return OSK_OK;
     }
+    if (n == "scan_tiles") {   // the view's scan tiles (the grid of its scan kernels)
+        *value = v->n_tiles;
+        return OSK_OK;
+    }
+    if (n == "seg_refs") {   // the references held on the view's segments, summed (readers, views, replicas)
+        int64_t refs = 0;
+        for (const osk_seg* sg : v->segs) refs += sg->refs.load();
+        *value = refs;
+        return OSK_OK;
+    }
     if (n == "mfma_full_tiles") {   // (root view only)
         std::lock_guard<std::mutex> lk(v->mu);
         unsigned long long c = 0;
@@ -2908,6 +3218,9 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
         {"sq6_rebound_gathered_rows", kCtrSq6GatheredRows, nullptr},
         {"sq6_rebound_passes", kCtrSq6ReboundPasses, nullptr},
         {"sq6_rebound_max_wg_cycles", kCtrSq6MaxWgCycles, nullptr},
+        {"sq6_tiles_own", kCtrSq6TilesOwn, nullptr},
+        {"sq6_tiles_by_others", kCtrSq6TilesByOthers, nullptr},
+        {"sq6_tiles_helped", kCtrSq6TilesHelped, nullptr},
         {"sq8_wide_events", kCtrWideEvents, nullptr},
         {"sq8_wide_pairs", kCtrWidePairs, nullptr},
         {"sq8_wide_wait_cycles", kCtrWideWaitCycles, nullptr},

@@ -147,7 +147,10 @@ enum Ctr : int {
     kCtrRowsSetupBarrierCycles = 20,
     kCtrRowsSetupFragmentCycles = 21,
     kCtrThrSettledRows = 22,       // thr_settle_f32: rows re-scored
-    kCtrCount = 24
+    kCtrSq6TilesOwn = 23,          // sq6_scan_shared: tiles this view's launches scanned for its own query
+    kCtrSq6TilesByOthers = 24,     // ...tiles of its queries that another view's launch had scanned
+    kCtrSq6TilesHelped = 25,       // ...(query, tile) pairs its launches scanned for other views
+    kCtrCount = 26
 };
 
 // What every prefilter scan kernel takes; each strategy's kernels take a struct derived from it, so a kernel
@@ -231,6 +234,25 @@ struct Sq8WideParams : Sq8Common {   // sq8_wide, sq8_wide_rows
     int wide_claim;                  // sq8_wide_rows: waves claim groups from a per-quarter counter (0: fixed interleave)
 };
 
+// A share group's slot (osk_sq6.hip sq6_scan_shared): the single query a view of the group has
+// in flight, posted on the view's stream before its scan (sq6_post: the fields first, then `gen` with an
+// agent-scope release).  A scan of the group serves the slots whose (slot, tile) word differs from `gen`.
+// gam, g2, cos_slack, cap6 and the tile tables are equal in every view of a group (its key) and come from
+// the serving launch's own parameters.
+constexpr int kShareSlots = 8;           // slots per group (osk_view::kMaxLeases)
+constexpr int kShareServe = 4;           // queries one pass over a tile scores at most
+struct alignas(128) Sq6Slot {
+    uint32_t gen;                    // 0 = nothing posted; published last
+    int32_t k;
+    unsigned long long seq;          // the group's post order (the longest-posted slots are served first)
+    const int4* q6;
+    const float4* qc6;
+    const float* qn_dev;
+    uint32_t* floor;
+    uint2* cand6;
+    int32_t* cnt6;
+};
+
 // sq6_pilot, sq6_scan, sq6_rebound (osk_sq6.hip): per segment, the 6-bit tiled codes and their bound terms; the
 // query's nibble split ([8C half-chunks][bh 4 dwords, bl 4 dwords]) and its 6-bit bound terms; the per-(query,
 // shard) floor buckets [q][n_shards][kFloorBuckets] (sortable lower bounds; rows8 / aux / q8 / qc are the int8
@@ -252,6 +274,14 @@ struct Sq6Params : Sq8Common {
     int rb_stride;                   // sq6_rebound: 1 = wave gw takes lists gw, gw + W, … (tune sq6_rebound_stride)
     int rb_wg_per_cu;                // sq6_rebound: workgroups per CU (0 = as many as fit; tune sq6_rebound_wgs)
     int rb_retest;                   // sq6_rebound: re-test candidates at the 6-bit level against the final floor
+    // sq6_scan_shared (null sh_slots: the private sq6_scan): the share group's slots and (slot, tile) words,
+    // this launch's own slot and generation, and the dispatch index below which it serves other slots
+    Sq6Slot* sh_slots;
+    uint32_t* sh_done;
+    int sh_slot;
+    uint32_t sh_gen;
+    int sh_limit;
+    int sh_idle;                     // 1: a workgroup whose own tile is done still serves the other slots (0: it exits)
 };
 
 struct SettleParams {
@@ -476,6 +506,13 @@ constexpr int kSq6Cap = 256;             // candidate rows per list between the 
 hipError_t launch_sq6_quantize(const float4* x, int64_t n, int units, int dim, void* out, float4* aux, hipStream_t s);
 hipError_t launch_sq6_scan(const Sq6Params& p, int dim, hipStream_t s, hipEvent_t ev_start = nullptr,
                            hipEvent_t ev_stop = nullptr);
+// The same search in the pieces a share group's call takes (osk_api.hip scan_sq6): the pilot, the post of the
+// view's slot (the descriptor, then its generation), the shared streaming pass, the re-bound.
+hipError_t launch_sq6_pilot(const Sq6Params& p, int dim, hipStream_t s);
+hipError_t launch_sq6_post(Sq6Slot* slot, const Sq6Slot& desc, hipStream_t s);
+hipError_t launch_sq6_scan_shared(const Sq6Params& p, int dim, hipStream_t s, hipEvent_t ev_start = nullptr,
+                                  hipEvent_t ev_stop = nullptr);
+hipError_t launch_sq6_rebound(const Sq6Params& p, int dim, hipStream_t s);
 hipError_t launch_sq8_settle(int cfg, int nq, const SettleParams& p, hipStream_t s);
 
 // The lane configs (osk_common.h, lane layout): cfg_index(units) picks the row of kCfgLV = {L, V} whose
@@ -531,6 +568,17 @@ struct Tuning {
     std::atomic<int> sq6_rebound_retest{1};   // sq6_rebound: the final-floor 6-bit re-test (0: gather every candidate)
     std::atomic<int> sq6_rebound_stride{1};   // sq6_rebound: strided list assignment (0: contiguous)
     std::atomic<int> sq6_rebound_wgs{0};      // sq6_rebound: workgroups per CU (0: as many as fit)
+    std::atomic<int> sq6_share{1};        // single queries in flight over one segment set share 6-bit corpus passes
+                                          // (sq6_scan_shared); 0 = every call its own sq6_scan
+    std::atomic<int> sq6_share_min_tiles{0};  // ...for views of at least this many tiles (0: more than one round of the
+                                          // chip's resident workgroups, CUs × tile_slots_per_cu)
+    std::atomic<int> sq6_share_idle{0};   // sq6_scan_shared: 1 = a workgroup whose own tile another pass has done still
+                                          // serves the other posted queries.  0: it exits, so a pass with nothing of its
+                                          // own to scan costs µs and the queries pile up for the next real pass (with 1
+                                          // every pass of the headline served exactly one query, someone else's:
+                                          // profiles/sq6_share/)
+    std::atomic<int> sq6_share_limit{-1}; // TESTING. a shared pass serves other views' queries only in the workgroups
+                                          // whose dispatch index is below this (-1: all)
     std::atomic<int> sq8_wide_rows{1};    // wide kernel, ≤ 128 dims: the main passes on sq8_wide_rows (0: sq8_wide)
     std::atomic<int> sq8_wide_rows_claim{1};   // sq8_wide_rows: dynamic group claims per quarter (0: wave + 8i)
     std::atomic<int> sq8_scan_deep{0};    // single-query sq8_scan ≤ 256 dims: U = 8 row groups in flight per wave

@@ -16,6 +16,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -213,6 +214,16 @@ struct osk_view {
     int64_t sq6_calls = 0;
     osk::DevBuf ws_q6, ws_qc6, ws_floor;              // its query (nibble split, bound terms), floor buckets,
     osk::DevBuf ws_cand6, ws_cnt6;                    // the streaming pass's candidates per list {row, 6-bit test}
+    // the share group of the views over this segment set with this tile table (osk_api.hip Sq6Group): joined at
+    // the view's first call that may share, left in the destructor; share_slot < 0: not in a group (none tried
+    // yet, or no free slot).  share_held (testing build): a call stopped after its post, for the resume entry.
+    std::vector<osk::TileDev> h_tiles;                // the tile table and its dispatch order (the group's key)
+    std::vector<int32_t> h_tile_order;
+    void* share_group = nullptr;
+    int share_slot = -1;
+    bool share_tried = false;
+    int share_stop = 0;                               // (testing build) 1: this call stops after its post
+    std::shared_ptr<void> share_held;
     // the tier's calibration (per segment, osk_seg::sq6_state): a probe call of this view counts its int8
     // re-bounds per segment into d_seg_rebound, copies them to h_seg_rebound on its stream and records
     // ev_probe; a later call folds them into the segments once the event has completed — nothing waits

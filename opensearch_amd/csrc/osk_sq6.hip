@@ -418,6 +418,289 @@ __global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq6Params p) {   // ≤ 12
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The shared streaming pass ("one pass for the queries in flight").  Views over one segment
+// set with equal tile tables form a share group (osk_api.hip); each view in the group posts its single query
+// in its slot before its scan (sq6_post, on the view's stream), and the group's scans run one after another
+// in enqueue order (an event chain).  A workgroup of a scan takes tile T, reads the slots, and scores every
+// posted query whose tile T is not done — its own first, then the longest-posted, at most kShareServe — against
+// one read of the tile: per query exactly sq6_scan's dots, floor, test, candidate list and bucket.  Then it
+// marks (slot, T) with the slot's generation; the owner's own scan, later in the chain, skips the tile.
+// A workgroup whose own tile is already done exits without serving anyone (tune sq6_share_idle 0): a pass
+// with no work of its own then costs microseconds and the waiting queries gather for the next pass that has
+// some.  Serving from such passes too was measured: every pass of the headline then scanned the whole corpus
+// for exactly one query, the next view's, and nothing was saved.
+//
+// The only hand-off between concurrent streams is the post: descriptor, agent-scope release, generation.  A
+// reader loads the generations with agent-scope loads, acquires once, and reads everything posted with
+// agent-scope loads (never the scalar path).  Tile words are written by one scan and read by later ones,
+// ordered by the kernel boundary and the event: no claims, no polling, nothing waits.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ T load_agent(const T* p) {   // a posted word: past this CU's L1 and this XCD's L2
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename T>
+__device__ __forceinline__ T* load_agent_ptr(T* const* p) {
+    return reinterpret_cast<T*>(load_agent(reinterpret_cast<const unsigned long long*>(p)));
+}
+
+// One wave: the slot's descriptor, then its generation (the publish: every shared word an agent-scope access,
+// the release between the payload and the flag, and the wait after the fence)
+__global__ __launch_bounds__(64) void sq6_post(Sq6Slot* slot, Sq6Slot d) {
+    if (threadIdx.x != 0) return;
+    __hip_atomic_store(&slot->k, d.k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&slot->seq, d.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long* w = reinterpret_cast<unsigned long long*>(&slot->q6);
+    const unsigned long long v[6] = {(unsigned long long)d.q6,    (unsigned long long)d.qc6,
+                                     (unsigned long long)d.qn_dev, (unsigned long long)d.floor,
+                                     (unsigned long long)d.cand6,  (unsigned long long)d.cnt6};
+#pragma unroll
+    for (int i = 0; i < 6; ++i) __hip_atomic_store(w + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(&slot->gen, d.gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// What a workgroup keeps in LDS per query it serves: the rarely used words (the loop keeps only the floor
+// state in registers)
+struct Sq6Served {
+    float4 qc6;
+    float qnd, sqn;
+    int k, slot;
+    uint32_t gen, pad;
+    uint32_t* floor;
+    uint2* cand6;
+    int32_t* cnt6;
+};
+
+template <int C, int U>
+__global__ __launch_bounds__(kBlock, 4) void sq6_scan_shared(Sq6Params p) {   // ≤ 128 VGPRs: 4 waves/SIMD
+    constexpr int R = 8, MQ = kShareServe;
+    __shared__ int4 s_q6[MQ][16 * C];   // the served queries' nibbles (sq6_scan's qh / ql, per half-chunk)
+    __shared__ Sq6Served s_sv[MQ];
+    __shared__ int s_n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: scalar loop control
+    const int t = lane & 7, g = lane >> 3;
+    const int tix = p.tile_order[blockIdx.x];
+    const int sim = p.sim;
+
+    // 1. pick the queries: lane s < kShareSlots of wave 0 looks at slot s
+    if (wave == 0) {
+        const bool in = lane < kShareSlots;
+        const bool own = lane == p.sh_slot;
+        uint32_t gen = in ? load_agent(&p.sh_slots[in ? lane : 0].gen) : 0u;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        if (own) gen = p.sh_gen;   // (posted on this stream before this launch)
+        uint32_t dn = 0u;
+        unsigned long long seq = 0ull;
+        if (in && gen) {
+            dn = load_agent(p.sh_done + (size_t)lane * p.n_tiles + tix);
+            seq = own ? 0ull : load_agent(&p.sh_slots[lane].seq);
+        }
+        bool need = in && gen != 0u && dn != gen && (own || (int)blockIdx.x < p.sh_limit);
+        if (!p.sh_idle && !((__ballot(need) >> p.sh_slot) & 1ull)) need = false;   // (own tile done: serve no one)
+        const uint64_t nm = __ballot(need);
+        // rank among the needed slots: the own query first (seq 0), then by post order
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < kShareSlots; ++j) {
+            const unsigned long long o = __shfl(seq, j);
+            rank += ((nm >> j) & 1ull) && (o < seq || (o == seq && j < lane));
+        }
+        const int n = min((int)__popcll(nm), MQ);
+        if (need && rank < MQ) {
+            const Sq6Slot* sl = p.sh_slots + lane;
+            Sq6Served sv;
+            sv.qc6 = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float* qcp = reinterpret_cast<const float*>(load_agent_ptr(&sl->qc6));
+            sv.qc6.x = load_agent(qcp);
+            sv.qc6.y = load_agent(qcp + 1);
+            sv.qc6.z = load_agent(qcp + 2);
+            sv.qc6.w = load_agent(qcp + 3);
+            sv.qnd = sim == SIM_COSINE ? load_agent(load_agent_ptr(&sl->qn_dev)) : 0.0f;
+            sv.sqn = sqrtf(sv.qnd);
+            sv.k = load_agent(&sl->k);
+            sv.slot = lane;
+            sv.gen = gen;
+            sv.pad = 0u;
+            sv.floor = load_agent_ptr(&sl->floor);
+            sv.cand6 = load_agent_ptr(&sl->cand6);
+            sv.cnt6 = load_agent_ptr(&sl->cnt6);
+            s_sv[rank] = sv;
+        }
+        if (lane == 0) {
+            s_n = n;
+            if (p.counters) {   // (one workgroup per tile: the view's share counters)
+                const bool own_need = (nm >> p.sh_slot) & 1ull;
+                atomicAdd(&p.counters[own_need ? kCtrSq6TilesOwn : kCtrSq6TilesByOthers], 1ull);
+                const int helped = n - (own_need ? 1 : 0);
+                if (helped > 0) atomicAdd(&p.counters[kCtrSq6TilesHelped], (unsigned long long)helped);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    const int nq = __builtin_amdgcn_readfirstlane(s_n);
+    if (nq == 0) return;   // (workgroup-uniform) every posted query's tile is done
+    // the served queries' nibbles → LDS (8-byte agent-scope loads)
+    for (int i = tid; i < nq * 32 * C; i += kBlock) {
+        const int qi = i / (32 * C), e = i - qi * (32 * C);
+        const Sq6Slot* sl = p.sh_slots + s_sv[qi].slot;
+        const unsigned long long* src = reinterpret_cast<const unsigned long long*>(load_agent_ptr(&sl->q6));
+        reinterpret_cast<unsigned long long*>(&s_q6[qi][0])[e] = load_agent(src + e);
+    }
+    __syncthreads();
+
+    const TileDev tile = p.tiles[tix];
+    const char* __restrict__ X6 = reinterpret_cast<const char*>(p.rows6[tile.seg]);
+    const float4* __restrict__ AX6 = p.aux6[tile.seg];
+    const int64_t rows = tile.row_end - tile.row_begin;
+    const int64_t per_wave = ((rows + 4 * R - 1) / (4 * R)) * R;
+    const int64_t wb = tile.row_begin + wave * per_wave;   // a multiple of 8: tiles start at multiples of 16
+    const int64_t we = min(wb + per_wave, tile.row_end);
+    const int list = tix * 4 + wave;
+    const size_t fb_off = (size_t)tile.shard * (kFloorBuckets + 1) * kFloorStride;
+
+    // per served query, sq6_scan's floor state (statically indexed: the loops over qi are unrolled)
+    uint64_t fkey[MQ];
+    uint32_t best[MQ], cv[MQ];
+    float tq0[MQ];
+    int nc[MQ];
+    auto set_floor = [&](int qi, uint32_t f32, uint64_t& fk, float& tq) {
+        uint64_t f = (uint64_t)f32 << 32;
+        if (!(key_score(f) > 0.0f)) f = 0ull;
+        if (f > fk) {
+            fk = f;
+            tq = sq8_quick(sim, fk, s_sv[qi].sqn, p.cos_slack);
+        }
+    };
+#pragma unroll
+    for (int qi = 0; qi < MQ; ++qi) {
+        fkey[qi] = 0ull;
+        best[qi] = 0u;
+        cv[qi] = 0u;
+        nc[qi] = 0;
+        tq0[qi] = sq8_quick(sim, 0ull, 0.0f, 0.0f);
+        if (qi < nq) {
+            uint32_t* fb = s_sv[qi].floor + fb_off;
+            const uint32_t v = load_agent(fb + lane * kFloorStride);
+            const uint32_t kth = wave_kth_largest(v, lane, s_sv[qi].k);
+            if ((list & (kFloorBuckets - 1)) == 0 && kth > 0u && lane == 0) atomicMax(fb + kFloorBuckets * kFloorStride, kth);
+            set_floor(qi, kth, fkey[qi], tq0[qi]);
+            cv[qi] = (uint32_t)__builtin_amdgcn_readfirstlane((int)load_agent(fb + kFloorBuckets * kFloorStride));
+        }
+    }
+
+    int it = 0;
+    for (int64_t r0 = wb; r0 < we; r0 += R * U, ++it) {
+        if (it < 4 || (it & 3) == 0) {
+#pragma unroll
+            for (int qi = 0; qi < MQ; ++qi)
+                if (qi < nq) {
+                    set_floor(qi, cv[qi], fkey[qi], tq0[qi]);
+                    cv[qi] = (uint32_t)__builtin_amdgcn_readfirstlane(
+                        (int)load_agent(s_sv[qi].floor + fb_off + kFloorBuckets * kFloorStride));
+                }
+        }
+        int4 hv[U][C];
+        int2 lv[U][C];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t gb = r0 + u * R;   // wave-uniform, 8-aligned
+            const char* blk = X6 + ((gb < we ? gb : wb) >> 3) * (int64_t)(1536 * C);
+#pragma unroll
+            for (int j = 0; j < C; ++j) {
+                hv[u][j] = load_i4_nt(reinterpret_cast<const int4*>(blk + j * 1024) + lane);
+                lv[u][j] = load_i2_nt(reinterpret_cast<const int2*>(blk + C * 1024 + j * 512) + lane);
+            }
+        }
+        const int64_t row = r0 + (int64_t)t * R + g;
+        const bool valid = t < U && row < we;
+        const float4 ax = AX6[valid ? row : wb];
+        if (!__ballot(valid)) continue;
+        const float sx = sim == SIM_COSINE ? __builtin_amdgcn_sqrtf(ax.w) : 0.0f;
+#pragma unroll
+        for (int qi = 0; qi < MQ; ++qi) {
+            if (qi >= nq) continue;   // wave-uniform
+            // the half-chunks outermost: one query half-chunk (8 dwords from LDS) is live at a time, and the U
+            // row groups' four sums (hh, hl, lh, ll) are the independent chains
+            int sum[U][4];
+#pragma unroll
+            for (int u = 0; u < U; ++u) sum[u][0] = sum[u][1] = sum[u][2] = sum[u][3] = 0;
+#pragma unroll
+            for (int j = 0; j < C; ++j) {
+                const int4 qa = s_q6[qi][(8 * j + t) * 2], qb = s_q6[qi][(8 * j + t) * 2 + 1];
+                const int qh[4] = {qa.x, qa.y, qa.z, qa.w}, ql[4] = {qb.x, qb.y, qb.z, qb.w};
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int hw[4] = {hv[u][j].x, hv[u][j].y, hv[u][j].z, hv[u][j].w};
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        sum[u][0] = __builtin_amdgcn_sdot8(hw[m], qh[m], sum[u][0], false);
+                        sum[u][1] = __builtin_amdgcn_sdot8(hw[m], ql[m], sum[u][1], false);
+                    }
+                    const int lw[2] = {lv[u][j].x, lv[u][j].y};
+#pragma unroll
+                    for (int w = 0; w < 2; ++w) {
+                        const int a = lw[w] & 0x33333333, b = (int)(((uint32_t)lw[w] >> 2) & 0x33333333u);
+                        sum[u][2] = __builtin_amdgcn_sdot8(a, qh[2 * w], sum[u][2], false);
+                        sum[u][2] = __builtin_amdgcn_sdot8(b, qh[2 * w + 1], sum[u][2], false);
+                        sum[u][3] = __builtin_amdgcn_sdot8(a, ql[2 * w], sum[u][3], false);
+                        sum[u][3] = __builtin_amdgcn_sdot8(b, ql[2 * w + 1], sum[u][3], false);
+                    }
+                }
+            }
+            int accu[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) accu[u] = 64 * sum[u][0] + 4 * sum[u][1] + 16 * sum[u][2] + sum[u][3];
+#pragma unroll
+            for (int u = 0; u < U; ++u) accu[u] = lane_sum<8>(accu[u]);
+            int acc = accu[0];
+#pragma unroll
+            for (int u = 1; u < U; ++u) acc = t == u ? accu[u] : acc;
+            const float4 qc6 = s_sv[qi].qc6;
+            const float side6 = sq8_bound_side(sim, (float)acc, ax, qc6, p.gam, p.g2);
+            const bool pass6 = valid && sq8_pass(sim, side6, side6, tq0[qi], sx);
+            const uint64_t pm = __ballot(pass6);
+            if (!pm) continue;   // wave-uniform: rare once the floor has risen
+            const int slot = nc[qi] + __popcll(pm & ((1ull << lane) - 1ull));
+            if (pass6) {
+                if (slot < p.cap6)
+                    (s_sv[qi].cand6 + (size_t)list * p.cap6)[slot] =
+                        make_uint2((uint32_t)row, __float_as_uint(cand6_value(sim, side6, sx)));
+                float lo, hi;
+                sq8_bounds(sim, (float)acc, ax, qc6, p.gam, p.g2, lo, hi);
+                best[qi] = max(best[qi], float_to_sortable(floor_lb_score(sim, lo, hi, s_sv[qi].qnd, ax.w, p.g2)));
+            }
+            nc[qi] += __popcll(pm);
+        }
+    }
+#pragma unroll
+    for (int qi = 0; qi < MQ; ++qi) {
+        if (qi >= nq) continue;
+        uint32_t b = best[qi];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o));
+        if (lane == 0) {
+            if (b > (uint32_t)(fkey[qi] >> 32))
+                atomicMax(s_sv[qi].floor + fb_off + (list & (kFloorBuckets - 1)) * kFloorStride, b);
+            s_sv[qi].cnt6[list] = nc[qi];
+        }
+    }
+    // 3. the tile is done for the served slots: every wave's stores drained, one release, then the words
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        for (int qi = 0; qi < nq; ++qi)
+            __hip_atomic_store(p.sh_done + (size_t)s_sv[qi].slot * p.n_tiles + tix, s_sv[qi].gen, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // The int8 re-bound pass.  Each list's candidates are first re-tested at the 6-bit level against the
 // shard's FINAL floor (the scan tested them against the floor as it stood when their tile ran, lower for
 // the tiles scanned first; sq8_pass is monotone in the threshold and the final floor is as valid as any
@@ -646,21 +929,49 @@ static const Sq6Fn kSq6[5] = {sq6_scan<2, 4>, sq6_scan<3, 3>, sq6_scan<4, 2>, sq
 static const Sq6Fn kSq6Pilot[5] = {sq6_pilot<2>, sq6_pilot<3>, sq6_pilot<4>, sq6_pilot<5>, sq6_pilot<6>};
 static const Sq6Fn kSq6Rebound[5] = {sq6_rebound<2>, sq6_rebound<3>, sq6_rebound<4>, sq6_rebound<5>, sq6_rebound<6>};
 
-// pilot → streaming pass → int8 re-bound pass; the profiling events bracket the streaming pass, the
-// dominant kernel whose roofline bench.py reports (the pilot and the re-bound read ≈ 2-3 % of its bytes)
-hipError_t launch_sq6_scan(const Sq6Params& p, int dim, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+static const Sq6Fn kSq6Shared[5] = {sq6_scan_shared<2, 4>, sq6_scan_shared<3, 3>, sq6_scan_shared<4, 2>,
+                                      sq6_scan_shared<5, 1>, sq6_scan_shared<6, 1>};
+
+static bool sq6_params_ok(const Sq6Params& p, int C) {
+    return C >= 2 && C <= 6 && p.q_count == 1 && p.q0 == 0 && p.k >= 1 && p.k <= kKQ && p.floor && p.q6 && p.cand6 &&
+           p.cnt6 && p.tile_order && p.cap6 >= 64 && p.cap6 <= kSq6Cap;
+}
+
+hipError_t launch_sq6_pilot(const Sq6Params& p, int dim, hipStream_t s) {
     const int C = sq6_chunks(dim);
-    if (C < 2 || C > 6 || p.q_count != 1 || p.k < 1 || p.k > kKQ || !p.floor || !p.q6 || !p.cand6 || !p.cnt6 ||
-        !p.tile_order || p.cap6 < 64 || p.cap6 > kSq6Cap)
-        return hipErrorInvalidValue;
+    if (!sq6_params_ok(p, C)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kSq6Pilot[C - 2], dim3(p.n_tiles), dim3(kBlock), 0, s, p);
-    const Sq6Fn scan = kSq6[C - 2];
+    return hipGetLastError();
+}
+
+hipError_t launch_sq6_post(Sq6Slot* slot, const Sq6Slot& desc, hipStream_t s) {
+    if (!slot || desc.gen == 0u || desc.seq == 0ull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sq6_post, dim3(1), dim3(64), 0, s, slot, desc);
+    return hipGetLastError();
+}
+
+// the streaming pass; the profiling events bracket it, the dominant kernel whose roofline bench.py reports
+// (the pilot and the re-bound read ≈ 2-3 % of its bytes)
+static hipError_t launch_sq6_pass(Sq6Fn scan, const Sq6Params& p, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
     if (ev_start || ev_stop)
         hipExtLaunchKernelGGL(scan, dim3(p.n_tiles), dim3(kBlock), 0, s, ev_start, ev_stop, 0, p);
     else
         hipLaunchKernelGGL(scan, dim3(p.n_tiles), dim3(kBlock), 0, s, p);
-    // the re-bound: persistent waves, a few lists each — as many workgroups per CU as fit at once (the
-    // kernel's registers decide: 4 at ≤ 128 VGPRs), so no wave waits for another's lists to finish
+    return hipGetLastError();
+}
+
+hipError_t launch_sq6_scan_shared(const Sq6Params& p, int dim, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    const int C = sq6_chunks(dim);
+    if (!sq6_params_ok(p, C) || !p.sh_slots || !p.sh_done || p.sh_slot < 0 || p.sh_slot >= kShareSlots || p.sh_gen == 0u)
+        return hipErrorInvalidValue;
+    return launch_sq6_pass(kSq6Shared[C - 2], p, s, ev_start, ev_stop);
+}
+
+// the re-bound: persistent waves, a few lists each — as many workgroups per CU as fit at once (the
+// kernel's registers decide: 4 at ≤ 128 VGPRs), so no wave waits for another's lists to finish
+hipError_t launch_sq6_rebound(const Sq6Params& p, int dim, hipStream_t s) {
+    const int C = sq6_chunks(dim);
+    if (!sq6_params_ok(p, C)) return hipErrorInvalidValue;
     const Sq6Fn rb = kSq6Rebound[C - 2];
     static std::atomic<int> s_fit[5];   // (zero-initialised; the same value from every thread)
     std::atomic<int>& fit_of = s_fit[C - 2];
@@ -677,6 +988,14 @@ hipError_t launch_sq6_scan(const Sq6Params& p, int dim, hipStream_t s, hipEvent_
     const int rb_grid = std::max(1, std::min(p.n_tiles, per_cu * (p.rb_cus > 0 ? p.rb_cus : 256)));
     hipLaunchKernelGGL(rb, dim3(rb_grid), dim3(kBlock), 0, s, p);
     return hipGetLastError();
+}
+
+// pilot → streaming pass → int8 re-bound pass (a call that shares nothing)
+hipError_t launch_sq6_scan(const Sq6Params& p, int dim, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+    hipError_t e = launch_sq6_pilot(p, dim, s);
+    if (e != hipSuccess) return e;
+    e = launch_sq6_pass(kSq6[sq6_chunks(dim) - 2], p, s, ev_start, ev_stop);
+    return e != hipSuccess ? e : launch_sq6_rebound(p, dim, s);
 }
 
 }  // namespace osk
