@@ -1792,9 +1792,17 @@ int32_t sq6_share_attach(osk_view* v) {
     return OSK_OK;
 }
 
-// Leave the group: after its last scan has completed (a scan may be writing this view's lists or reading its
-// posted query), the slot's generation word is cleared so no later scan reads the descriptor; the group goes
-// with its last view.
+// Withdraw a slot's posted query (caller holds grp->mu, which keeps later scans out; the group's device is
+// current): behind the group's last pass, which may be reading the query or writing its view's lists, the
+// slot's generation word is cleared so no later pass reads the descriptor.
+void sq6_share_withdraw(Sq6Group* grp, int slot) {
+    if (grp->has_last) (void)hipEventSynchronize(grp->last);
+    (void)hipMemset(&grp->d_slots[slot].gen, 0, sizeof(uint32_t));
+    (void)hipStreamSynchronize(nullptr);
+}
+
+// Leave the group: after its last scan has completed the view's query is withdrawn; the group goes with its
+// last view.
 void sq6_share_detach(osk_view* v) {
     Sq6Group* grp = static_cast<Sq6Group*>(v->share_group);
     if (!grp) return;
@@ -1806,9 +1814,7 @@ void sq6_share_detach(osk_view* v) {
         // lock is not held over the wait, so other groups attach and detach meanwhile (the group itself stays:
         // this view is still attached)
         std::lock_guard<std::mutex> lk(grp->mu);
-        if (grp->has_last) (void)hipEventSynchronize(grp->last);
-        (void)hipMemset(&grp->d_slots[v->share_slot].gen, 0, sizeof(uint32_t));
-        (void)hipStreamSynchronize(nullptr);
+        sq6_share_withdraw(grp, v->share_slot);
     }
     bool last_view = false;
     {
@@ -2181,11 +2187,9 @@ int32_t sq6_share_scan(const Sq8Call& c, const Sq6Params& p) {
         if (e == hipSuccess) e = launch_sq6_scan_shared(p, v->dim, c.st, launch_ev_start(v, 0), launch_ev_stop(v, 0, c.nq));
         if (e == hipSuccess) e = hipEventRecord(grp->last, c.st);
         if (e != hipSuccess) {
-            // the query is posted but its pass is not coming: withdraw it, behind the passes that may be reading
-            // it, so no later pass writes this view's lists while another call of the view uses them
-            if (grp->has_last) (void)hipEventSynchronize(grp->last);
-            (void)hipMemset(&grp->d_slots[v->share_slot].gen, 0, sizeof(uint32_t));
-            (void)hipStreamSynchronize(nullptr);
+            // the query is posted but its pass is not coming: withdraw it, so no later pass writes this view's
+            // lists while another call of the view uses them
+            sq6_share_withdraw(grp, v->share_slot);
             OSK_HIP(e);
         }
         grp->has_last = true;

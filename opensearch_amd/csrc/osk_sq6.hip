@@ -9,7 +9,7 @@
 // too wide to build the settle's lists from directly (on isotropic 768-dim data ≈ 1.9 % of a C3 shard's
 // rows reach the re-score and 8 % of the lists overflow).  So the 6-bit pass only filters, against a
 // per-(query, shard) FLOOR, and the int8 copy re-bounds what passes:
-//   sq6_pilot    the first 8 rows of every scan wave (2 % of the rows) on the int8 copy: their lower
+//   sq6_pilot    the first 4 rows of every scan wave (1 % of the rows) on the int8 copy: their lower
 //                bounds seed 64 floor buckets per shard (bucket = wave list mod 64, atomicMax);
 //   sq6_scan     streams the 6-bit codes; a row whose 6-bit upper bound is below the floor T = the k-th
 //                best of the 64 bucket maxima is dropped (T ≤ the shard's k-th best exact score, so it
@@ -140,14 +140,25 @@ hipError_t launch_sq6_quantize(const float4* x, int64_t n, int units, int dim, v
 }
 
 // ------------------------------------------------------------------------------------------------
-// the three kernels of a 6-bit search (one query).  A scan row is 8 lanes; a wave takes 8 rows (one
-// block) per row group and U groups per iteration (≈ U·4.6 KiB in flight per wave at C = 3); the row
-// split per wave is sq8_scan's with R = 8, and each wave's list is list = tile·4 + wave.
+// the kernels of a 6-bit search (one query).  A scan row is 8 lanes; a wave takes 8 rows (one block) per
+// row group and U groups per iteration (≈ U·4.6 KiB in flight per wave at C = 3).  First the pieces they
+// share: sq6_scan and sq6_scan_shared differ only in where a query lives (registers / LDS) and their dot loops.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int2 load_i2_nt(const int2* p) {
     typedef int i2v __attribute__((ext_vector_type(2)));
     const i2v v = __builtin_nontemporal_load(reinterpret_cast<const i2v*>(p));
     return make_int2(v.x, v.y);
+}
+
+// A word other workgroups or streams write while this kernel runs (the floor cells and buckets, a posted
+// query): read past this CU's L1 and this XCD's L2, never on the scalar path
+template <typename T>
+__device__ __forceinline__ T load_agent(const T* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename T>
+__device__ __forceinline__ T* load_agent_ptr(T* const* p) {
+    return reinterpret_cast<T*>(load_agent(reinterpret_cast<const unsigned long long*>(p)));
 }
 
 // The k-th largest of the 64 lanes' values (k ≤ 64): each lane ranks its value against every lane's
@@ -161,6 +172,11 @@ __device__ __forceinline__ uint32_t wave_kth_largest(uint32_t v, int lane, int k
     }
     const uint64_t hit = __ballot(rank == k - 1);
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)__builtin_ctzll(hit));
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
 }
 
 // A lower bound of the exact score of a row whose raw device-order value is ≥ lo (dot kinds) or whose d²
@@ -178,67 +194,6 @@ __device__ __forceinline__ float floor_lb_score(int sim, float lo, float hi, flo
     return fmaxf((1.0f + c) * 0.5f, 0.0f) * (1.0f - 0x1p-18f);
 }
 
-// Sampled int8 lower bounds seed the floor before the streaming pass: each wave scores the first 4 rows
-// of its range (the 6-bit pass's split) on the int8 copy (16 lanes per row, exact device-order norms)
-// and raises its floor bucket (list mod 64) to the best of them.
-template <int C>
-__global__ __launch_bounds__(kBlock) void sq6_pilot(Sq6Params p) {
-    constexpr int R = 8;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: scalar loop control
-    const int cg = lane >> 4, ct = lane & 15;
-    const int tix = p.tile_order[blockIdx.x];
-    const TileDev tile = p.tiles[tix];
-    const SegDev seg = p.segs[tile.seg];
-    const int4* __restrict__ X8 = p.rows8[tile.seg];
-    const int sim = p.sim, u8 = p.units8;
-    const int64_t rows = tile.row_end - tile.row_begin;
-    const int64_t per_wave = ((rows + 4 * R - 1) / (4 * R)) * R;
-    const int64_t wb = tile.row_begin + wave * per_wave;
-    const int64_t we = min(wb + per_wave, tile.row_end);
-    const float4 qc = p.qc[0];
-    const float qnd = sim == SIM_COSINE ? p.qn_dev[0] : 0.0f;
-    // the first 4 rows of the wave's range (1 % of the rows), 16 lanes each (u8 ≤ 16·C units: C per lane)
-    constexpr int H = 1;
-    int4 xv[H][C], qv[C];
-    float4 ax[H];
-    float xnd[H] = {0.0f};
-    bool v[H];
-#pragma unroll
-    for (int i = 0; i < C; ++i) qv[i] = ct + 16 * i < u8 ? p.q8[ct + 16 * i] : make_int4(0, 0, 0, 0);
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-        const int64_t r = wb + 4 * h + cg;
-        v[h] = r < we;
-        const int64_t rc = v[h] ? r : tile.row_begin;
-        const int4* xr = X8 + rc * u8;
-#pragma unroll
-        for (int i = 0; i < C; ++i) xv[h][i] = ct + 16 * i < u8 ? xr[ct + 16 * i] : make_int4(0, 0, 0, 0);
-        ax[h] = p.aux[tile.seg][rc];
-        if (sim == SIM_COSINE) xnd[h] = seg.xnorm_f[rc];
-    }
-    uint32_t best = 0u;
-#pragma unroll
-    for (int h = 0; h < H; ++h) {
-        int a8 = 0;
-#pragma unroll
-        for (int i = 0; i < C; ++i) {
-            a8 = __builtin_amdgcn_sdot4(xv[h][i].x, qv[i].x, a8, false);
-            a8 = __builtin_amdgcn_sdot4(xv[h][i].y, qv[i].y, a8, false);
-            a8 = __builtin_amdgcn_sdot4(xv[h][i].z, qv[i].z, a8, false);
-            a8 = __builtin_amdgcn_sdot4(xv[h][i].w, qv[i].w, a8, false);
-        }
-        a8 = lane_sum<16>(a8);
-        float lo, hi;
-        sq8_bounds(sim, (float)a8, ax[h], qc, p.gam, p.g2, lo, hi);
-        const float lb = sim == SIM_EUCLIDEAN ? score_f32_l2(hi) : score_f32(sim, lo, qnd, xnd[h]);
-        if (v[h]) best = max(best, float_to_sortable(lb));
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o));
-    uint32_t* fb = p.floor + ((size_t)p.q0 * p.n_shards + tile.shard) * (kFloorBuckets + 1) * kFloorStride;
-    if (lane == 0 && best) atomicMax(fb + ((tix * 4 + wave) & (kFloorBuckets - 1)) * kFloorStride, best);
-}
-
 // A candidate's 6-bit test in one float, for the re-bound's re-test against the final floor's quick
 // threshold tq (cand6_keep): the bound side itself (EUCLIDEAN: keep unless v > tq; dot kinds: unless v < tq),
 // COSINE the side over √|x|² rounded up (keep unless v < tq: never stricter than the real-valued
@@ -253,12 +208,194 @@ __device__ __forceinline__ bool cand6_keep(int sim, float v, float tq) {
     return sim == SIM_EUCLIDEAN ? !(v > tq) : !(v < tq);
 }
 
+// A wave's share of a tile: sq8_scan's row split with R = 8 (wb a multiple of 8: tiles start at multiples
+// of 16) and the wave's list.  The pilot, both scans and the re-bound's list table agree on it.
+struct Sq6Wave {
+    int64_t wb, we;
+    int list;
+};
+__device__ __forceinline__ Sq6Wave sq6_wave(const TileDev& tile, int tix, int wave) {
+    constexpr int R = 8;
+    const int64_t rows = tile.row_end - tile.row_begin;
+    const int64_t per_wave = ((rows + 4 * R - 1) / (4 * R)) * R;
+    const int64_t wb = tile.row_begin + wave * per_wave;
+    return Sq6Wave{wb, min(wb + per_wave, tile.row_end), tix * 4 + wave};
+}
+
+// A (query, shard)'s floor words: kFloorBuckets bucket maxima (a list's bucket is list mod 64), then the
+// cell: the max of the k-th values computed so far
+__device__ __forceinline__ uint32_t* sq6_floor_of(uint32_t* floor, int q0, int n_shards, int shard) {
+    return floor + ((size_t)q0 * n_shards + shard) * (kFloorBuckets + 1) * kFloorStride;
+}
+__device__ __forceinline__ uint32_t* sq6_floor_bucket(uint32_t* fb, int list) {
+    return fb + (list & (kFloorBuckets - 1)) * kFloorStride;
+}
+__device__ __forceinline__ uint32_t* sq6_floor_cell(uint32_t* fb) { return fb + kFloorBuckets * kFloorStride; }
+
+// The k-th best of the shard's buckets as they stand (every lane gets it); where `publish`, the cell is
+// raised to it.  At the start of a scan wave only one wave in 64 publishes: all of a round's waves start
+// together, and thousands of atomics on one address would queue for 100+ µs.
+__device__ __forceinline__ uint32_t sq6_floor_kth(uint32_t* fb, int lane, int k, bool publish) {
+    const uint32_t kth = wave_kth_largest(load_agent(fb + lane * kFloorStride), lane, k);
+    if (publish && kth > 0u && lane == 0) atomicMax(sq6_floor_cell(fb), kth);
+    return kth;
+}
+
+// A wave's view of one (query, shard) floor: the key (a score that is not positive is no floor) and its
+// quick threshold.  In a scan the key only rises (raise); the re-bound sets it per shard (set).  (sqn by
+// reference: the shared pass keeps it in LDS and reads it only when the floor does rise.)
+struct Sq6Floor {
+    uint64_t fkey;
+    float tq;
+    static __device__ __forceinline__ uint64_t key_of(uint32_t sortable) {
+        const uint64_t f = (uint64_t)sortable << 32;
+        return key_score(f) > 0.0f ? f : 0ull;
+    }
+    __device__ __forceinline__ void set(int sim, uint32_t sortable, const float& sqn, float cos_slack) {
+        fkey = key_of(sortable);
+        tq = sq8_quick(sim, fkey, sqn, cos_slack);
+    }
+    __device__ __forceinline__ void raise(int sim, uint32_t sortable, const float& sqn, float cos_slack) {
+        if (key_of(sortable) > fkey) set(sim, sortable, sqn, cos_slack);
+    }
+};
+
+// What the test needs of a query: in registers (sq6_scan) or in LDS (sq6_scan_shared)
+struct Sq6Query {
+    float4 qc6;
+    float qnd, sqn;
+    uint2* cand6;   // [list][cap6]
+};
+
+// The U row groups of an iteration: unconditional non-temporal loads from a clamped in-range block (masked
+// after): see sq8_scan
+template <int C, int U>
+__device__ __forceinline__ void sq6_load_groups(const char* __restrict__ X6, int64_t r0, const Sq6Wave& w, int lane,
+                                                int4 (&hv)[U][C], int2 (&lv)[U][C]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int64_t gb = r0 + u * 8;   // wave-uniform, 8-aligned
+        const char* blk = X6 + ((gb < w.we ? gb : w.wb) >> 3) * (int64_t)(1536 * C);
+#pragma unroll
+        for (int j = 0; j < C; ++j) {
+            hv[u][j] = load_i4_nt(reinterpret_cast<const int4*>(blk + j * 1024) + lane);
+            lv[u][j] = load_i2_nt(reinterpret_cast<const int2*>(blk + C * 1024 + j * 512) + lane);
+        }
+    }
+}
+
+// A lane's nibble sums Σh·bh, Σh·bl, Σl·bh, Σl·bl of a row → its share of the row's exact int32 dot
+__device__ __forceinline__ int sq6_weigh(int hh, int hl, int lh, int ll) { return 64 * hh + 4 * hl + 16 * lh + ll; }
+// The lanes' shares → the rows' dots, group u's row g gathered to lane (g, t = u): the tests then run once
+// per iteration instead of once per group
+template <int U>
+__device__ __forceinline__ int sq6_gather(int (&accu)[U], int t) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) accu[u] = lane_sum<8>(accu[u]);
+    int acc = accu[0];
+#pragma unroll
+    for (int u = 1; u < U; ++u) acc = t == u ? accu[u] : acc;
+    return acc;
+}
+
+// The test the certificate rests on, for one query and the wave's rows of one iteration (one row per valid
+// lane, its 6-bit dot acc and bound terms ax): the 6-bit bound's upper side against the floor's quick
+// threshold tq; the rows that pass are appended to the list's candidate buffer with their test value (the
+// re-bound re-tests them) and their 6-bit lower bounds go into best.  nc counts every passing row, stored or
+// not.  (no_cand, no_store, no_lb: the testing build's timing ablations.)
+__device__ __forceinline__ void sq6_test_emit(int sim, int acc, float4 ax, float sx, bool valid, int64_t row, int lane,
+                                              const Sq6Query& q, float gam, float g2, float tq, int list, int cap6,
+                                              int& nc, uint32_t& best, bool no_cand = false, bool no_store = false,
+                                              bool no_lb = false) {
+    const float4 qc6 = q.qc6;
+    const float side6 = sq8_bound_side(sim, (float)acc, ax, qc6, gam, g2);
+    const bool pass6 = valid && sq8_pass(sim, side6, side6, tq, sx);
+    const uint64_t pm = __ballot(pass6);
+    if (!pm || no_cand) return;   // wave-uniform: rare once the floor has risen
+    const int slot = nc + __popcll(pm & ((1ull << lane) - 1ull));
+    if (pass6) {
+        if (slot < cap6 && !no_store)
+            (q.cand6 + (size_t)list * cap6)[slot] =
+                make_uint2((uint32_t)row, __float_as_uint(cand6_value(sim, side6, sx)));
+        if (!no_lb) {
+            float lo, hi;
+            sq8_bounds(sim, (float)acc, ax, qc6, gam, g2, lo, hi);
+            best = max(best, float_to_sortable(floor_lb_score(sim, lo, hi, q.qnd, ax.w, g2)));
+        }
+    }
+    nc += __popcll(pm);
+}
+
+// A scan wave's end for one query: its best lower bound raises its bucket, once, for the later rounds of
+// workgroups (only if it can still lift the floor: same-address atomics queue at L2), and its count is
+// stored (cnt6: the query's [n_lists]; visited rows and the re-bound counter: sq6_rebound)
+__device__ __forceinline__ void sq6_wave_end(uint32_t best, int nc, const Sq6Floor& fl, uint32_t* fb, int list,
+                                             int32_t* cnt6, int lane) {
+    best = wave_max(best);
+    if (lane == 0) {
+        if (best > (uint32_t)(fl.fkey >> 32)) atomicMax(sq6_floor_bucket(fb, list), best);
+        cnt6[list] = nc;
+    }
+}
+
+// The int8 copy on 16 lanes per row (the pilot and the re-bound; u8 ≤ 16·C units, C per lane): a lane's
+// units of a row or of the query, the row's int8 interval, and the lower-bound score with exact
+// device-order norms
+template <int C>
+__device__ __forceinline__ void sq6_load_units(const int4* src, int ct, int u8, int4 (&v)[C]) {
+#pragma unroll
+    for (int i = 0; i < C; ++i) v[i] = ct + 16 * i < u8 ? src[ct + 16 * i] : make_int4(0, 0, 0, 0);
+}
+template <int C>
+__device__ __forceinline__ void sq6_int8_bounds(int sim, const int4 (&xv)[C], const int4 (&qv)[C], float4 ax, float4 qc,
+                                                float gam, float g2, float& lo, float& hi) {
+    int a8 = 0;
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        a8 = __builtin_amdgcn_sdot4(xv[i].x, qv[i].x, a8, false);
+        a8 = __builtin_amdgcn_sdot4(xv[i].y, qv[i].y, a8, false);
+        a8 = __builtin_amdgcn_sdot4(xv[i].z, qv[i].z, a8, false);
+        a8 = __builtin_amdgcn_sdot4(xv[i].w, qv[i].w, a8, false);
+    }
+    sq8_bounds(sim, (float)lane_sum<16>(a8), ax, qc, gam, g2, lo, hi);
+}
+__device__ __forceinline__ float sq6_int8_lb(int sim, float lo, float hi, float qnd, float xnd) {
+    return sim == SIM_EUCLIDEAN ? score_f32_l2(hi) : score_f32(sim, lo, qnd, xnd);
+}
+
+// Sampled int8 lower bounds seed the floor before the streaming pass: each wave scores the first 4 rows
+// of its range (the 6-bit pass's split; 1 % of the rows) on the int8 copy and raises its floor bucket to
+// the best of them.
+template <int C>
+__global__ __launch_bounds__(kBlock) void sq6_pilot(Sq6Params p) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: scalar loop control
+    const int cg = lane >> 4, ct = lane & 15;
+    const int tix = p.tile_order[blockIdx.x];
+    const TileDev tile = p.tiles[tix];
+    const SegDev seg = p.segs[tile.seg];
+    const int sim = p.sim, u8 = p.units8;
+    const Sq6Wave w = sq6_wave(tile, tix, wave);
+    const float4 qc = p.qc[0];
+    const float qnd = sim == SIM_COSINE ? p.qn_dev[0] : 0.0f;
+    int4 xv[C], qv[C];
+    sq6_load_units<C>(p.q8, ct, u8, qv);
+    const int64_t r = w.wb + cg;
+    const bool v = r < w.we;
+    const int64_t rc = v ? r : tile.row_begin;
+    sq6_load_units<C>(p.rows8[tile.seg] + rc * u8, ct, u8, xv);
+    const float4 ax = p.aux[tile.seg][rc];
+    const float xnd = sim == SIM_COSINE ? seg.xnorm_f[rc] : 0.0f;
+    float lo, hi;
+    sq6_int8_bounds<C>(sim, xv, qv, ax, qc, p.gam, p.g2, lo, hi);
+    const uint32_t best = wave_max(v ? float_to_sortable(sq6_int8_lb(sim, lo, hi, qnd, xnd)) : 0u);
+    if (lane == 0 && best) atomicMax(sq6_floor_bucket(sq6_floor_of(p.floor, p.q0, p.n_shards, tile.shard), w.list), best);
+}
+
 // The streaming pass: 6-bit dot of every row, the 6-bit bound's upper side against the shard's floor,
 // and the rows that pass appended to the wave's candidate buffer (cand6[list][cap6]: {row, its 6-bit test
-// value (cand6_value)}, count in cnt6;
-// cnt6 > cap6 = overflowed) for the int8 re-bound pass.  A row dropped here has ub6 < T ≤ the shard's
-// k-th best exact score: it cannot enter the top k.  The best 6-bit lower bound among a wave's passing
-// rows raises its floor bucket as the pass goes (a distinct row per bucket, as for the pilot's).
+// value (cand6_value)}, count in cnt6; cnt6 > cap6 = overflowed) for the int8 re-bound pass.  A row dropped
+// here has ub6 < T ≤ the shard's k-th best exact score: it cannot enter the top k.  The best 6-bit lower bound
+// among a wave's passing rows raises its floor bucket (a distinct row per bucket, as for the pilot's).
 template <int C, int U>
 __global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq6Params p) {   // ≤ 128 VGPRs: 4 waves/SIMD
     constexpr int R = 8;
@@ -284,72 +421,41 @@ __global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq6Params p) {   // ≤ 12
         qh[j][0] = a.x; qh[j][1] = a.y; qh[j][2] = a.z; qh[j][3] = a.w;
         ql[j][0] = b.x; ql[j][1] = b.y; ql[j][2] = b.z; ql[j][3] = b.w;
     }
-    const float4 qc6 = p.qc6[0];
     const float qnd0 = sim == SIM_COSINE ? p.qn_dev[0] : 0.0f;
-    const float sqn0 = sqrtf(qnd0);
+    const Sq6Query q{p.qc6[0], qnd0, sqrtf(qnd0), p.cand6};
 
-    const int64_t rows = tile.row_end - tile.row_begin;
-    const int64_t per_wave = ((rows + 4 * R - 1) / (4 * R)) * R;
-    const int64_t wb = tile.row_begin + wave * per_wave;   // a multiple of 8: tiles start at multiples of 16
-    const int64_t we = min(wb + per_wave, tile.row_end);
-
-    const int list = tix * 4 + wave;
-    uint32_t* fb = p.floor + ((size_t)p.q0 * p.n_shards + tile.shard) * (kFloorBuckets + 1) * kFloorStride;
-    uint2* cbuf = p.cand6 + (size_t)list * p.cap6;
-    uint64_t fkey = 0ull;
+    const Sq6Wave w = sq6_wave(tile, tix, wave);
+    uint32_t* fb = sq6_floor_of(p.floor, p.q0, p.n_shards, tile.shard);
+    Sq6Floor fl;
+    fl.set(sim, 0u, q.sqn, p.cos_slack);
     uint32_t best = 0u;
-    float tq0 = sq8_quick(sim, 0ull, 0.0f, 0.0f);
     int nc = 0, it = 0;
-    uint32_t* cell = fb + kFloorBuckets * kFloorStride;   // the shard's floor: max of the k-th values computed
-    auto set_floor = [&](uint32_t f32) {
-        uint64_t f = (uint64_t)f32 << 32;
-        if (!(key_score(f) > 0.0f)) f = 0ull;
-        if (f > fkey) {
-            fkey = f;
-            tq0 = sq8_quick(sim, fkey, sqn0, p.cos_slack);
-        }
-    };
-    // k-th best of the buckets now (the pilot's and earlier tiles' bounds) → the cell and this wave
-    auto recompute = [&](bool write) {
-        const uint32_t v = __hip_atomic_load(fb + lane * kFloorStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t kth = wave_kth_largest(v, lane, p.k);
-        if (write && kth > (uint32_t)(fkey >> 32) && lane == 0) atomicMax(cell, kth);
-        set_floor(kth);
-    };
-    // at the start every wave computes the k-th itself but only one wave in 64 writes the cell: all of a
-    // round's waves start together, and thousands of atomics on one address would queue for 100+ µs
-    if (!(ablate & 2)) recompute((list & (kFloorBuckets - 1)) == 0);
+    // the floor as the buckets stand now (the pilot's and earlier tiles' bounds) → the cell and this wave
+    if (!(ablate & 2)) fl.raise(sim, sq6_floor_kth(fb, lane, p.k, (w.list & (kFloorBuckets - 1)) == 0), q.sqn, p.cos_slack);
     // then the cell is re-read every iteration for the first four, every fourth later (one load, issued
     // a refresh ahead).  A wave publishes its best lower bound to its bucket once, at its end, for the
     // later rounds of workgroups: publishing and re-ranking inside the loop (same-address atomics queue at
     // L2, and the ranking's registers spilled the loop's scalars) left the re-bound count unchanged at C3
     // and cost ≈ 10 % of the pass (profiles/r03c/sq6_ablate_r3.jsonl)
-    uint32_t cv = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t cv = load_agent(sq6_floor_cell(fb));
+    // (a by-reference lambda, as this kernel always had: without one hipcc proves the row pointers global and
+    // schedules the loop's loads differently — a change of its own to measure, profiles/sq6_factor/README.md)
+    auto refresh = [&]() {
+        fl.raise(sim, cv, q.sqn, p.cos_slack);
+        cv = load_agent(sq6_floor_cell(fb));
+    };
 
-    for (int64_t r0 = wb; r0 < we; r0 += R * U, ++it) {
-        if ((it < 4 || (it & 3) == 0) && !(ablate & 2)) {
-            set_floor(cv);
-            cv = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+    for (int64_t r0 = w.wb; r0 < w.we; r0 += R * U, ++it) {
+        if ((it < 4 || (it & 3) == 0) && !(ablate & 2)) refresh();
         int4 hv[U][C];
         int2 lv[U][C];
-        // unconditional loads from a clamped in-range block (masked after): see sq8_scan
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t gb = r0 + u * R;   // wave-uniform, 8-aligned
-            const char* blk = X6 + ((gb < we ? gb : wb) >> 3) * (int64_t)(1536 * C);
-#pragma unroll
-            for (int j = 0; j < C; ++j) {
-                hv[u][j] = load_i4_nt(reinterpret_cast<const int4*>(blk + j * 1024) + lane);
-                lv[u][j] = load_i2_nt(reinterpret_cast<const int2*>(blk + C * 1024 + j * 512) + lane);
-            }
-        }
+        sq6_load_groups<C, U>(X6, r0, w, lane, hv, lv);
         // the tests run once per iteration, lane (g, t < U) on group t's row g (the U groups' sums are
         // gathered to those lanes below): one bound term load, one test and at most one candidate block
         // per iteration instead of U — their latency sits between this wave's loads
         const int64_t row = r0 + (int64_t)t * R + g;
-        const bool valid = t < U && row < we;
-        const float4 ax = AX6[valid ? row : wb];
+        const bool valid = t < U && row < w.we;
+        const float4 ax = AX6[valid ? row : w.wb];
         // every group's dot first, then the bounds and tests: the four v_dot8 chains of a group are serial
         // dependencies, and with the tests (ballot, branch) between groups the compiler could not overlap
         // one group's chains with the next one's (36 % of the wave cycles were issue stalls)
@@ -374,48 +480,23 @@ __global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq6Params p) {   // ≤ 12
                 }
                 const int lw[2] = {lv[u][j].x, lv[u][j].y};
 #pragma unroll
-                for (int w = 0; w < 2; ++w) {
-                    const int a = lw[w] & 0x33333333, b = (int)(((uint32_t)lw[w] >> 2) & 0x33333333u);
-                    lh[0] = __builtin_amdgcn_sdot8(a, qh[j][2 * w], lh[0], false);
-                    lh[1] = __builtin_amdgcn_sdot8(b, qh[j][2 * w + 1], lh[1], false);
-                    ll[0] = __builtin_amdgcn_sdot8(a, ql[j][2 * w], ll[0], false);
-                    ll[1] = __builtin_amdgcn_sdot8(b, ql[j][2 * w + 1], ll[1], false);
+                for (int w2 = 0; w2 < 2; ++w2) {
+                    const int a = lw[w2] & 0x33333333, b = (int)(((uint32_t)lw[w2] >> 2) & 0x33333333u);
+                    lh[0] = __builtin_amdgcn_sdot8(a, qh[j][2 * w2], lh[0], false);
+                    lh[1] = __builtin_amdgcn_sdot8(b, qh[j][2 * w2 + 1], lh[1], false);
+                    ll[0] = __builtin_amdgcn_sdot8(a, ql[j][2 * w2], ll[0], false);
+                    ll[1] = __builtin_amdgcn_sdot8(b, ql[j][2 * w2 + 1], ll[1], false);
                 }
             }
-            accu[u] = 64 * (hh[0] + hh[1]) + 4 * (hl[0] + hl[1]) + 16 * (lh[0] + lh[1]) + (ll[0] + ll[1]);
+            accu[u] = sq6_weigh(hh[0] + hh[1], hl[0] + hl[1], lh[0] + lh[1], ll[0] + ll[1]);
         }
-#pragma unroll
-        for (int u = 0; u < U; ++u) accu[u] = lane_sum<8>(accu[u]);
-        int acc = accu[0];
-#pragma unroll
-        for (int u = 1; u < U; ++u) acc = t == u ? accu[u] : acc;
-        const uint64_t vm = __ballot(valid);
-        if (!vm) continue;
+        const int acc = sq6_gather<U>(accu, t);
+        if (!__ballot(valid)) continue;
         const float sx = sim == SIM_COSINE ? __builtin_amdgcn_sqrtf(ax.w) : 0.0f;   // (1 ulp ≪ the quick test's slack)
-        const float side6 = sq8_bound_side(sim, (float)acc, ax, qc6, p.gam, p.g2);
-        const bool pass6 = valid && sq8_pass(sim, side6, side6, tq0, sx);
-        const uint64_t pm = __ballot(pass6);
-        if (!pm || (ablate & 1)) continue;   // wave-uniform: rare once the floor has risen
-        // the passing rows (one lane per row) → the candidate buffer, and their 6-bit lower bounds
-        const int slot = nc + __popcll(pm & ((1ull << lane) - 1ull));
-        if (pass6) {
-            if (slot < p.cap6 && !(ablate & 4)) {   // the row and its 6-bit test inputs (the re-bound re-tests)
-                cbuf[slot] = make_uint2((uint32_t)row, __float_as_uint(cand6_value(sim, side6, sx)));
-            }
-            if (!(ablate & 8)) {
-                float lo, hi;
-                sq8_bounds(sim, (float)acc, ax, qc6, p.gam, p.g2, lo, hi);
-                best = max(best, float_to_sortable(floor_lb_score(sim, lo, hi, qnd0, ax.w, p.g2)));
-            }
-        }
-        nc += __popcll(pm);
+        sq6_test_emit(sim, acc, ax, sx, valid, row, lane, q, p.gam, p.g2, fl.tq, w.list, p.cap6, nc, best,
+                      (ablate & 1) != 0, (ablate & 4) != 0, (ablate & 8) != 0);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o));
-    if (lane == 0) {
-        if (best > (uint32_t)(fkey >> 32)) atomicMax(fb + (list & (kFloorBuckets - 1)) * kFloorStride, best);
-        p.cnt6[(size_t)p.q0 * p.n_lists + list] = nc;   // (visited rows and the re-bound counter: sq6_rebound)
-    }
+    sq6_wave_end(best, nc, fl, fb, w.list, p.cnt6 + (size_t)p.q0 * p.n_lists, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -424,8 +505,9 @@ __global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq6Params p) {   // ≤ 12
 // in its slot before its scan (sq6_post, on the view's stream), and the group's scans run one after another
 // in enqueue order (an event chain).  A workgroup of a scan takes tile T, reads the slots, and scores every
 // posted query whose tile T is not done — its own first, then the longest-posted, at most kShareServe — against
-// one read of the tile: per query exactly sq6_scan's dots, floor, test, candidate list and bucket.  Then it
-// marks (slot, T) with the slot's generation; the owner's own scan, later in the chain, skips the tile.
+// one read of the tile: per query exactly sq6_scan's dots, floor, test, candidate list and bucket (the same
+// functions; only the dot loop is this kernel's own).  Then it marks (slot, T) with the slot's generation;
+// the owner's own scan, later in the chain, skips the tile.
 // A workgroup whose own tile is already done exits without serving anyone (tune sq6_share_idle 0): a pass
 // with no work of its own then costs microseconds and the waiting queries gather for the next pass that has
 // some.  Serving from such passes too was measured: every pass of the headline then scanned the whole corpus
@@ -436,14 +518,6 @@ __global__ __launch_bounds__(kBlock, 4) void sq6_scan(Sq6Params p) {   // ≤ 12
 // agent-scope loads (never the scalar path).  Tile words are written by one scan and read by later ones,
 // ordered by the kernel boundary and the event: no claims, no polling, nothing waits.
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ T load_agent(const T* p) {   // a posted word: past this CU's L1 and this XCD's L2
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-__device__ __forceinline__ T* load_agent_ptr(T* const* p) {
-    return reinterpret_cast<T*>(load_agent(reinterpret_cast<const unsigned long long*>(p)));
-}
 
 // One wave: the slot's descriptor, then its generation (the publish: every shared word an agent-scope access,
 // the release between the payload and the flag, and the wait after the fence)
@@ -465,13 +539,10 @@ __global__ __launch_bounds__(64) void sq6_post(Sq6Slot* slot, Sq6Slot d) {
 
 // What a workgroup keeps in LDS per query it serves: the rarely used words (the loop keeps only the floor
 // state in registers)
-struct Sq6Served {
-    float4 qc6;
-    float qnd, sqn;
+struct Sq6Served : Sq6Query {
     int k, slot;
     uint32_t gen, pad;
     uint32_t* floor;
-    uint2* cand6;
     int32_t* cnt6;
 };
 
@@ -553,72 +624,44 @@ __global__ __launch_bounds__(kBlock, 4) void sq6_scan_shared(Sq6Params p) {   //
     }
     __syncthreads();
 
+    // 2. the wave's rows, for every served query (statically indexed state: the loops over qi are unrolled)
     const TileDev tile = p.tiles[tix];
     const char* __restrict__ X6 = reinterpret_cast<const char*>(p.rows6[tile.seg]);
     const float4* __restrict__ AX6 = p.aux6[tile.seg];
-    const int64_t rows = tile.row_end - tile.row_begin;
-    const int64_t per_wave = ((rows + 4 * R - 1) / (4 * R)) * R;
-    const int64_t wb = tile.row_begin + wave * per_wave;   // a multiple of 8: tiles start at multiples of 16
-    const int64_t we = min(wb + per_wave, tile.row_end);
-    const int list = tix * 4 + wave;
-    const size_t fb_off = (size_t)tile.shard * (kFloorBuckets + 1) * kFloorStride;
-
-    // per served query, sq6_scan's floor state (statically indexed: the loops over qi are unrolled)
-    uint64_t fkey[MQ];
-    uint32_t best[MQ], cv[MQ];
-    float tq0[MQ];
-    int nc[MQ];
-    auto set_floor = [&](int qi, uint32_t f32, uint64_t& fk, float& tq) {
-        uint64_t f = (uint64_t)f32 << 32;
-        if (!(key_score(f) > 0.0f)) f = 0ull;
-        if (f > fk) {
-            fk = f;
-            tq = sq8_quick(sim, fk, s_sv[qi].sqn, p.cos_slack);
-        }
+    const Sq6Wave w = sq6_wave(tile, tix, wave);
+    auto fb_of = [&](int qi) {   // (a posted query is its call's only one: q0 = 0)
+        return sq6_floor_of(s_sv[qi].floor, 0, p.n_shards, tile.shard);
     };
+    Sq6Floor fl[MQ];
+    uint32_t best[MQ] = {}, cv[MQ] = {};
+    int nc[MQ] = {};
 #pragma unroll
     for (int qi = 0; qi < MQ; ++qi) {
-        fkey[qi] = 0ull;
-        best[qi] = 0u;
-        cv[qi] = 0u;
-        nc[qi] = 0;
-        tq0[qi] = sq8_quick(sim, 0ull, 0.0f, 0.0f);
+        fl[qi].set(sim, 0u, 0.0f, 0.0f);   // (no floor yet: sqn and the slack are not read)
         if (qi < nq) {
-            uint32_t* fb = s_sv[qi].floor + fb_off;
-            const uint32_t v = load_agent(fb + lane * kFloorStride);
-            const uint32_t kth = wave_kth_largest(v, lane, s_sv[qi].k);
-            if ((list & (kFloorBuckets - 1)) == 0 && kth > 0u && lane == 0) atomicMax(fb + kFloorBuckets * kFloorStride, kth);
-            set_floor(qi, kth, fkey[qi], tq0[qi]);
-            cv[qi] = (uint32_t)__builtin_amdgcn_readfirstlane((int)load_agent(fb + kFloorBuckets * kFloorStride));
+            uint32_t* fb = fb_of(qi);
+            fl[qi].raise(sim, sq6_floor_kth(fb, lane, s_sv[qi].k, (w.list & (kFloorBuckets - 1)) == 0), s_sv[qi].sqn,
+                         p.cos_slack);
+            cv[qi] = (uint32_t)__builtin_amdgcn_readfirstlane((int)load_agent(sq6_floor_cell(fb)));
         }
     }
 
     int it = 0;
-    for (int64_t r0 = wb; r0 < we; r0 += R * U, ++it) {
+    for (int64_t r0 = w.wb; r0 < w.we; r0 += R * U, ++it) {
         if (it < 4 || (it & 3) == 0) {
 #pragma unroll
             for (int qi = 0; qi < MQ; ++qi)
                 if (qi < nq) {
-                    set_floor(qi, cv[qi], fkey[qi], tq0[qi]);
-                    cv[qi] = (uint32_t)__builtin_amdgcn_readfirstlane(
-                        (int)load_agent(s_sv[qi].floor + fb_off + kFloorBuckets * kFloorStride));
+                    fl[qi].raise(sim, cv[qi], s_sv[qi].sqn, p.cos_slack);
+                    cv[qi] = (uint32_t)__builtin_amdgcn_readfirstlane((int)load_agent(sq6_floor_cell(fb_of(qi))));
                 }
         }
         int4 hv[U][C];
         int2 lv[U][C];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t gb = r0 + u * R;   // wave-uniform, 8-aligned
-            const char* blk = X6 + ((gb < we ? gb : wb) >> 3) * (int64_t)(1536 * C);
-#pragma unroll
-            for (int j = 0; j < C; ++j) {
-                hv[u][j] = load_i4_nt(reinterpret_cast<const int4*>(blk + j * 1024) + lane);
-                lv[u][j] = load_i2_nt(reinterpret_cast<const int2*>(blk + C * 1024 + j * 512) + lane);
-            }
-        }
+        sq6_load_groups<C, U>(X6, r0, w, lane, hv, lv);
         const int64_t row = r0 + (int64_t)t * R + g;
-        const bool valid = t < U && row < we;
-        const float4 ax = AX6[valid ? row : wb];
+        const bool valid = t < U && row < w.we;
+        const float4 ax = AX6[valid ? row : w.wb];
         if (!__ballot(valid)) continue;
         const float sx = sim == SIM_COSINE ? __builtin_amdgcn_sqrtf(ax.w) : 0.0f;
 #pragma unroll
@@ -643,52 +686,25 @@ __global__ __launch_bounds__(kBlock, 4) void sq6_scan_shared(Sq6Params p) {   //
                     }
                     const int lw[2] = {lv[u][j].x, lv[u][j].y};
 #pragma unroll
-                    for (int w = 0; w < 2; ++w) {
-                        const int a = lw[w] & 0x33333333, b = (int)(((uint32_t)lw[w] >> 2) & 0x33333333u);
-                        sum[u][2] = __builtin_amdgcn_sdot8(a, qh[2 * w], sum[u][2], false);
-                        sum[u][2] = __builtin_amdgcn_sdot8(b, qh[2 * w + 1], sum[u][2], false);
-                        sum[u][3] = __builtin_amdgcn_sdot8(a, ql[2 * w], sum[u][3], false);
-                        sum[u][3] = __builtin_amdgcn_sdot8(b, ql[2 * w + 1], sum[u][3], false);
+                    for (int w2 = 0; w2 < 2; ++w2) {
+                        const int a = lw[w2] & 0x33333333, b = (int)(((uint32_t)lw[w2] >> 2) & 0x33333333u);
+                        sum[u][2] = __builtin_amdgcn_sdot8(a, qh[2 * w2], sum[u][2], false);
+                        sum[u][2] = __builtin_amdgcn_sdot8(b, qh[2 * w2 + 1], sum[u][2], false);
+                        sum[u][3] = __builtin_amdgcn_sdot8(a, ql[2 * w2], sum[u][3], false);
+                        sum[u][3] = __builtin_amdgcn_sdot8(b, ql[2 * w2 + 1], sum[u][3], false);
                     }
                 }
             }
             int accu[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) accu[u] = 64 * sum[u][0] + 4 * sum[u][1] + 16 * sum[u][2] + sum[u][3];
-#pragma unroll
-            for (int u = 0; u < U; ++u) accu[u] = lane_sum<8>(accu[u]);
-            int acc = accu[0];
-#pragma unroll
-            for (int u = 1; u < U; ++u) acc = t == u ? accu[u] : acc;
-            const float4 qc6 = s_sv[qi].qc6;
-            const float side6 = sq8_bound_side(sim, (float)acc, ax, qc6, p.gam, p.g2);
-            const bool pass6 = valid && sq8_pass(sim, side6, side6, tq0[qi], sx);
-            const uint64_t pm = __ballot(pass6);
-            if (!pm) continue;   // wave-uniform: rare once the floor has risen
-            const int slot = nc[qi] + __popcll(pm & ((1ull << lane) - 1ull));
-            if (pass6) {
-                if (slot < p.cap6)
-                    (s_sv[qi].cand6 + (size_t)list * p.cap6)[slot] =
-                        make_uint2((uint32_t)row, __float_as_uint(cand6_value(sim, side6, sx)));
-                float lo, hi;
-                sq8_bounds(sim, (float)acc, ax, qc6, p.gam, p.g2, lo, hi);
-                best[qi] = max(best[qi], float_to_sortable(floor_lb_score(sim, lo, hi, s_sv[qi].qnd, ax.w, p.g2)));
-            }
-            nc[qi] += __popcll(pm);
+            for (int u = 0; u < U; ++u) accu[u] = sq6_weigh(sum[u][0], sum[u][1], sum[u][2], sum[u][3]);
+            sq6_test_emit(sim, sq6_gather<U>(accu, t), ax, sx, valid, row, lane, s_sv[qi], p.gam, p.g2, fl[qi].tq, w.list,
+                          p.cap6, nc[qi], best[qi]);
         }
     }
 #pragma unroll
-    for (int qi = 0; qi < MQ; ++qi) {
-        if (qi >= nq) continue;
-        uint32_t b = best[qi];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o));
-        if (lane == 0) {
-            if (b > (uint32_t)(fkey[qi] >> 32))
-                atomicMax(s_sv[qi].floor + fb_off + (list & (kFloorBuckets - 1)) * kFloorStride, b);
-            s_sv[qi].cnt6[list] = nc[qi];
-        }
-    }
+    for (int qi = 0; qi < MQ; ++qi)
+        if (qi < nq) sq6_wave_end(best[qi], nc[qi], fl[qi], fb_of(qi), w.list, s_sv[qi].cnt6, lane);
     // 3. the tile is done for the served slots: every wave's stores drained, one release, then the words
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -738,12 +754,11 @@ __global__ __launch_bounds__(kBlock) void sq6_rebound(Sq6Params p) {
     const float qnd0 = sim == SIM_COSINE ? p.qn_dev[0] : 0.0f;
     const float sqn0 = sqrtf(qnd0);
     int4 qv8[C];   // this lane's units of the int8 query
-#pragma unroll
-    for (int i = 0; i < C; ++i) qv8[i] = ct + 16 * i < u8 ? p.q8[ct + 16 * i] : make_int4(0, 0, 0, 0);
+    sq6_load_units<C>(p.q8, ct, u8, qv8);
     const size_t cnt_base = (size_t)p.q0 * p.n_lists;
     auto shard_floor = [&](int shard) -> uint32_t {   // the k-th best bucket maximum, or the floor cell
-        const uint32_t* fb = p.floor + ((size_t)p.q0 * p.n_shards + shard) * (kFloorBuckets + 1) * kFloorStride;
-        return max(wave_kth_largest(fb[lane * kFloorStride], lane, p.k), fb[kFloorBuckets * kFloorStride]);
+        uint32_t* fb = sq6_floor_of(p.floor, p.q0, p.n_shards, shard);   // (final: plain loads)
+        return max(wave_kth_largest(fb[lane * kFloorStride], lane, p.k), *sq6_floor_cell(fb));
     };
     if (floor_lds)
         for (int s = wave; s < p.n_shards; s += 4) {
@@ -766,8 +781,7 @@ __global__ __launch_bounds__(kBlock) void sq6_rebound(Sq6Params p) {
         d.c64 = p.cand6[(size_t)l * p.cap6 + lane];
     };
     int cur_shard = -1, cur_seg = -1;
-    uint64_t fkey = 0ull;
-    float tqf = 0.0f;   // the final floor's quick threshold (the 6-bit re-test)
+    Sq6Floor fl{0ull, 0.0f};   // the shard's final floor and its quick threshold (the 6-bit re-test)
     const int4* X8 = nullptr;
     const float4* AX8 = nullptr;
     const float* XN = nullptr;
@@ -809,9 +823,7 @@ __global__ __launch_bounds__(kBlock) void sq6_rebound(Sq6Params p) {
         }
         if (tile.shard != cur_shard) {   // the shard's final floor
             cur_shard = tile.shard;
-            fkey = (uint64_t)(floor_lds ? s_floor[tile.shard] : shard_floor(tile.shard)) << 32;
-            if (!(key_score(fkey) > 0.0f)) fkey = 0ull;
-            tqf = sq8_quick(sim, fkey, sqn0, p.cos_slack);
+            fl.set(sim, floor_lds ? s_floor[tile.shard] : shard_floor(tile.shard), sqn0, p.cos_slack);
         }
         if ((list & 3) == 0) vis += (unsigned long long)(tile.row_end - tile.row_begin);   // (each tile once)
         reb += (unsigned long long)nc;
@@ -826,14 +838,14 @@ __global__ __launch_bounds__(kBlock) void sq6_rebound(Sq6Params p) {
                 uint2 c = d.c64;
                 if (c0 > 0 && c0 + lane < nc) c = p.cand6[(size_t)list * p.cap6 + c0 + lane];
                 const uint32_t r = c.x;
-                const bool keep = c0 + lane < nc && (!p.rb_retest || cand6_keep(sim, __uint_as_float(c.y), tqf));
+                const bool keep = c0 + lane < nc && (!p.rb_retest || cand6_keep(sim, __uint_as_float(c.y), fl.tq));
                 const uint64_t km = __ballot(keep);
                 if (keep)
                     sel[ns + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u))] = r;
                 ns += __popcll(km);
             }
             gathered += (unsigned long long)ns;
-            float tq0 = tqf;
+            float tq0 = fl.tq;
             // 8 survivors per pass (two halves of 4 rows × 16 lanes), every load of a pass issued before any
             // is used
             for (int c0 = 0; c0 < ns; c0 += 8) {
@@ -852,34 +864,22 @@ __global__ __launch_bounds__(kBlock) void sq6_rebound(Sq6Params p) {
                 float xnd[2] = {0.0f, 0.0f};
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const int4* xr = X8 + (int64_t)r[h] * u8;
-#pragma unroll
-                    for (int i = 0; i < C; ++i) xv[h][i] = ct + 16 * i < u8 ? xr[ct + 16 * i] : make_int4(0, 0, 0, 0);
+                    sq6_load_units<C>(X8 + (int64_t)r[h] * u8, ct, u8, xv[h]);
                     ax[h] = AX8[r[h]];
                     if (sim == SIM_COSINE) xnd[h] = XN[r[h]];
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    int a8 = 0;
-#pragma unroll
-                    for (int i = 0; i < C; ++i) {
-                        const int4 qv = qv8[i];
-                        a8 = __builtin_amdgcn_sdot4(xv[h][i].x, qv.x, a8, false);
-                        a8 = __builtin_amdgcn_sdot4(xv[h][i].y, qv.y, a8, false);
-                        a8 = __builtin_amdgcn_sdot4(xv[h][i].z, qv.z, a8, false);
-                        a8 = __builtin_amdgcn_sdot4(xv[h][i].w, qv.w, a8, false);
-                    }
-                    a8 = lane_sum<16>(a8);
                     float lo, hi;
-                    sq8_bounds(sim, (float)a8, ax[h], qc, p.gam, p.g2, lo, hi);
+                    sq6_int8_bounds<C>(sim, xv[h], qv8, ax[h], qc, p.gam, p.g2, lo, hi);
                     const float sx = sim == SIM_COSINE ? __builtin_amdgcn_sqrtf(ax[h].w) : 0.0f;
                     const bool pass = v[h] && sq8_pass(sim, lo, hi, tq0, sx);
                     if (__ballot(pass && ct == 0)) {
                         const float ub = sim == SIM_EUCLIDEAN ? score_f32_l2(lo) : score_f32(sim, hi, qnd0, xnd[h]);
-                        const float lb = sim == SIM_EUCLIDEAN ? score_f32_l2(hi) : score_f32(sim, lo, qnd0, xnd[h]);
+                        const float lb = sq6_int8_lb(sim, lo, hi, qnd0, xnd[h]);
                         const uint64_t key = pass ? make_key(ub, vbase + r[h]) : 0ull;
                         wave_offer2(key, float_to_sortable(lb), pass && ct == 0, lk0, lp0, thr0, lane, kKQ);
-                        tq0 = sq8_quick(sim, max(thr0, fkey), sqn0, p.cos_slack);
+                        tq0 = sq8_quick(sim, max(thr0, fl.fkey), sqn0, p.cos_slack);
                     }
                 }
             }
@@ -887,9 +887,7 @@ __global__ __launch_bounds__(kBlock) void sq6_rebound(Sq6Params p) {
             lk0 = ~0ull;   // overflowed: above every threshold → the settle re-scans the list's rows exactly
             lp0 = 0u;
         }
-        uint32_t m = (lane < kKQ && lk0 && lk0 != ~0ull) ? lp0 : 0u;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+        const uint32_t m = wave_max((lane < kKQ && lk0 && lk0 != ~0ull) ? lp0 : 0u);
         const size_t l = cnt_base + list;
         if (lane < kKQ) {
             p.cand[l * kKQ + lane] = lk0;

@@ -87,7 +87,7 @@ def close_all(ds, readers):
         r.close()
 
 
-@pytest.mark.parametrize("dim", [512, 520, 600, 768, 1000, 1024, 1536, 2048])
+@pytest.mark.parametrize("dim", [512, 520, 600, 768, 1000, 1024, 1184, 1200, 1280, 1536, 2048])
 @pytest.mark.parametrize("sim", SIMS, ids=lambda s: s.name)
 def test_single_queries_equal_int8_fp32_and_oracle(dim, sim):
     n = 2600 + dim % 13
@@ -97,7 +97,7 @@ def test_single_queries_equal_int8_fp32_and_oracle(dim, sim):
     try:
         before = ds.counter("sq6_calls")
         s, d, sh, c, t, _ = three_ways(lambda q: ds.search(q, 10, 0, 10), queries)
-        has_tier = dim in (512, 768, 1000, 1024, 1536)
+        has_tier = dim in (512, 768, 1000, 1024, 1200, 1280, 1536)
         # the tier exists where 6-bit rows are ≤ 0.8 × the int8 rows (dims padded to 256 per lane set)
         assert (ds.counter("sq6_calls") - before == len(queries)) == has_tier
         for i in range(len(queries)):

@@ -8,8 +8,8 @@ on the shards without a sparse field with the oracle.  The testing build splits 
 (osk_testing_sq6_post / osk_testing_sq6_resume) so that who scans what is deterministic, and
 `sq6_share_limit` bounds the workgroups that serve other views.
 
-Shapes: 60k rows of 512, 768 and 1536 dims (C = 2, 3, 6) in three ragged segments over three shards, one with
-a sparse field, 40 tiles; all four similarities; k 1, 10 and 12.
+Shapes: 60k rows of 512, 768, 1024, 1280 and 1536 dims (C = 2, 3, 4, 5, 6: every instantiation) in three ragged
+segments over three shards, one with a sparse field, 40 tiles; all four similarities; k 1, 10 and 12.
 """
 import ctypes as C
 
@@ -163,7 +163,7 @@ def delta(after, before):
     return tuple(a - b for a, b in zip(after, before))
 
 
-SHAPES = [(768, s) for s in SIMS] + [(512, COS), (1536, DOT)]
+SHAPES = [(768, s) for s in SIMS] + [(512, COS), (1024, COS), (1280, DOT), (1536, DOT)]
 IDS = [f"{d}-{s.name}" for d, s in SHAPES]
 
 
@@ -196,7 +196,8 @@ def test_all_helped(T, dim, sim):
 
 
 @pytest.mark.parametrize("limit", ["half", 1])
-@pytest.mark.parametrize("dim,sim", [(768, COS), (512, COS), (1536, DOT)], ids=["768-COSINE", "512-COSINE", "1536-DOT"])
+@pytest.mark.parametrize("dim,sim", [(768, COS), (512, COS), (1280, DOT), (1536, DOT)],
+                         ids=["768-COSINE", "512-COSINE", "1280-DOT", "1536-DOT"])
 def test_split(T, dim, sim, limit):
     """sq6_share_limit X: A serves the others in its first X workgroups only; each finishes the rest itself."""
     w = world(T, dim, sim)

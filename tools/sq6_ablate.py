@@ -1,5 +1,5 @@
-"""A/B timing of the 6-bit prefilter tier at C3 (8 × 1.25M × 768 COSINE, single queries): the int8 scan
-(sq8_scan) against the 6-bit scan (sq6_scan) and its ablations (tune sq8_mfma_ablate in the testing
+"""A/B timing of the 6-bit prefilter tier (8 × RPS × DIM COSINE, single queries; by default C3: 8 × 1.25M × 768,
+other shapes from the environment: RPS, DIM, N queries): the int8 scan (sq8_scan) against the 6-bit scan (sq6_scan) and its ablations (tune sq8_mfma_ablate in the testing
 build: 1 drop the int8 re-bound queue, 2 no floor, 3 both — results wrong, kernel time only).
 Prints one JSON line per variant: mean scan launch (HIP events, osk_view_scan_time), int8 re-bounds
 and exactly re-scored rows per query."""
@@ -16,7 +16,7 @@ from opensearch_amd import _lib, distributed as D  # noqa: E402
 from opensearch_amd._lib import check, lib  # noqa: E402
 
 RPS = int(os.environ.get("RPS", "1250000"))
-DIM, K, N = 768, 10, int(os.environ.get("N", "40"))
+DIM, K, N = int(os.environ.get("DIM", "768")), 10, int(os.environ.get("N", "40"))
 for kv in filter(None, os.environ.get("TUNE", "").split(",")):
     _lib.tune(kv.split("=")[0], int(kv.split("=")[1]))
 torch.cuda.set_device(0)
