@@ -1,6 +1,7 @@
 // osk_api.hip — the C-ABI of libosknn.so (declared in include/osknn.h): segments, views, the
 // single-device search paths and the coordinator merge.  The object model (osk_seg, osk_view) is in
-// osk_objects.h; the multi-GPU exchange (osk_comm, RCCL) in osk_comm.hip.
+// osk_objects.h, its lifetime and the built-once structures in osk_derived.hip; the multi-GPU exchange
+// (osk_comm, RCCL) in osk_comm.hip.
 // Every entry point catches all C++ exceptions and returns an error code (see osknn.h).
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -131,170 +132,7 @@ hipStream_t device_stream(int device) {
     return g_streams[device];
 }
 
-
-// The device view of a view's segments (pointers re-read: staging may add row norms later).
-std::vector<SegDev> seg_devs(const osk_view* v) {
-    std::vector<SegDev> sd(v->segs.size());
-    for (size_t i = 0; i < v->segs.size(); ++i) {
-        const osk_seg* s = v->segs[i];
-        sd[i] = SegDev{s->d_rows, s->d_xnorm_f, s->d_xnorm_i, s->d_ord_to_doc, s->n_rows,
-                       v->seg_doc_base[i], v->seg_shard[i]};
-    }
-    return sd;
-}
-
 }  // namespace osk
-
-namespace {
-void sq6_forget_segment(const osk_seg* sg);   // (below, with the 6-bit tier's in-flight records)
-void sq6_share_detach(osk_view* v);           // (below, with the share groups)
-}
-
-osk_seg::~osk_seg() {
-    if (self_view) delete self_view;   // holds no reference on this segment
-    if (d_rows) (void)hipFree(d_rows);
-    if (d_xnorm_f) (void)hipFree(d_xnorm_f);
-    if (d_xnorm_i) (void)hipFree(d_xnorm_i);
-    if (d_ord_to_doc) (void)hipFree(d_ord_to_doc);
-    if (d_split) (void)hipFree(d_split);
-    if (d_maxnorm2) (void)hipFree(d_maxnorm2);
-    if (d_xsqrt) (void)hipFree(d_xsqrt);
-    if (d_q8) (void)hipFree(d_q8);
-    if (d_q8aux) (void)hipFree(d_q8aux);
-    if (d_q8t) (void)hipFree(d_q8t);
-    if (d_q8auxt) (void)hipFree(d_q8auxt);
-    if (d_q8w) (void)hipFree(d_q8w);
-    if (d_row_parent) (void)hipFree(d_row_parent);
-    if (d_q6 || d_q6aux) {   // stream-ordered pool allocations (ensure_sq8_seg); the hipFree calls above
-        int cur = -1;         // synchronised the device, so nothing reads them any more
-        (void)hipGetDevice(&cur);
-        (void)hipSetDevice(device);
-        if (d_q6) (void)hipFreeAsync(d_q6, nullptr);
-        if (d_q6aux) (void)hipFreeAsync(d_q6aux, nullptr);
-        (void)hipStreamSynchronize(nullptr);
-        if (cur >= 0) (void)hipSetDevice(cur);
-    }
-    sq6_forget_segment(this);   // (a later segment at this address must not wait on this one's launches)
-}
-
-int64_t osk_seg::hbm_bytes() const {
-    const int64_t n = std::max<int64_t>(1, n_rows);
-    int64_t b = n * units * 16;
-    if (d_xnorm_f) b += n * 4;
-    if (d_xnorm_i) b += n * 4;
-    if (d_ord_to_doc) b += n * 4;
-    if (d_split) b += std::max<int64_t>(1, (n_rows + 127) / 128) * 8 * split_KS * 2 * 1024 + n * 4 + 4;
-    if (d_q8) b += n * units8 * 16 + n * 16;
-    if (d_q8t) b += std::max<int64_t>(1, (n_rows + 15) / 16) * sq8_mfma_ks(units8) * 1024;
-    if (d_q8auxt) b += std::max<int64_t>(1, (n_rows + 15) / 16) * kAuxGroupF4 * 16;
-    if (d_q8w) b += std::max<int64_t>(1, (n_rows + 15) / 16) * sq8_wide_ks(units8) * 1024;
-    if (d_q6) b += sq6_bytes(n_rows, dim);
-    if (d_row_parent) b += n * 4;
-    return b;
-}
-
-osk_view::~osk_view() {
-    for (osk_view* r : replicas) delete r;   // (no lease is live: the caller's release contract)
-    sq6_share_detach(this);   // (waits for the group's scans: they may be writing this view's lists)
-    for (hipStream_t st : lease_streams)
-        if (st) (void)hipStreamDestroy(st);
-    if (xs_event) (void)hipEventDestroy(xs_event);
-    if (ev_probe) {   // a calibration read-back may still be landing in h_seg_rebound
-        if (probe_pending) (void)hipEventSynchronize(ev_probe);
-        (void)hipEventDestroy(ev_probe);
-    }
-    for (hipEvent_t e : ev_call)
-        if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < kEvRing; ++i) {
-        if (ev_start[i]) (void)hipEventDestroy(ev_start[i]);
-        if (ev_stop[i]) (void)hipEventDestroy(ev_stop[i]);
-    }
-    if (holds_refs)
-        for (osk_seg* s : segs) osk::seg_unref(s);
-}
-
-void osk::seg_unref(osk_seg* s) {
-    if (s && s->refs.fetch_sub(1) == 1) {
-        (void)hipSetDevice(s->device);
-        delete s;
-    }
-}
-
-namespace {
-
-int32_t ensure_sq8_seg(osk_seg* s, hipStream_t st);
-int32_t ensure_sq8t_seg(osk_seg* s, hipStream_t st, bool wide);
-int32_t ensure_split(osk_seg* s, hipStream_t st);
-int32_t ensure_sq8(osk_view* v, hipStream_t st);
-int32_t ensure_sq8t(osk_view* v, hipStream_t st);
-int32_t ensure_sq8w(osk_view* v, hipStream_t st);
-int32_t ensure_mfma(osk_view* v, hipStream_t st);
-int32_t ensure_nested(osk_view* v, hipStream_t st);
-
-int32_t seg_finish(osk_seg* s, const int32_t* ord_to_doc, hipStream_t st) {
-    // row norms
-    if (s->enc == ENC_FLOAT32 && s->sim == SIM_COSINE) {
-        OSK_HIP(hipMalloc(&s->d_xnorm_f, std::max<int64_t>(1, s->n_rows) * sizeof(float)));
-        if (s->n_rows > 0)
-            OSK_HIP(launch_row_norms_f32(static_cast<const float4*>(s->d_rows), s->n_rows, s->units,
-                                         s->cfg, s->d_xnorm_f, st));
-    }
-    if (s->enc == ENC_BYTE) {
-        OSK_HIP(hipMalloc(&s->d_xnorm_i, std::max<int64_t>(1, s->n_rows) * sizeof(int32_t)));
-        if (s->n_rows > 0)
-            OSK_HIP(launch_row_norms_i8(static_cast<const int4*>(s->d_rows), s->n_rows, s->units,
-                                        s->d_xnorm_i, st));
-    }
-    if (ord_to_doc) {
-        for (int64_t i = 0; i < s->n_rows; ++i) {
-            if (ord_to_doc[i] < 0 || ord_to_doc[i] >= s->max_doc ||
-                (i > 0 && ord_to_doc[i] <= ord_to_doc[i - 1])) {
-                set_error("ord_to_doc must be strictly ascending docIDs in [0, max_doc)");
-                return OSK_ERR_INVALID;
-            }
-        }
-        OSK_HIP(hipMalloc(&s->d_ord_to_doc, std::max<int64_t>(1, s->n_rows) * sizeof(int32_t)));
-        OSK_HIP(hipMemcpyAsync(s->d_ord_to_doc, ord_to_doc, s->n_rows * sizeof(int32_t),
-                               hipMemcpyHostToDevice, st));
-    }
-    OSK_HIP(hipStreamSynchronize(st));
-    // the certified int8 prefilter copy is the default path of float32 searches: built with the segment
-    // (staging = the reader's constructor / warmer, S/index/engine/InternalEngine.java:2409-2432), so
-    // no search pays for it and the segment's HBM footprint is known at staging
-    if (s->enc == ENC_FLOAT32) return ensure_sq8_seg(s, st);
-    return OSK_OK;
-}
-
-int32_t seg_alloc(int device, int64_t n_rows, int dim, int enc, int sim, int max_doc,
-                  const int32_t* ord_to_doc, std::unique_ptr<osk_seg>& out) {
-    OSK_REQUIRE(n_rows >= 0, "n_rows must be >= 0");
-    OSK_REQUIRE(dim >= 1 && dim <= OSK_MAX_DIM, "dim must be in [1, 4096]");
-    OSK_REQUIRE(enc == ENC_FLOAT32 || enc == ENC_BYTE, "unknown encoding");
-    OSK_REQUIRE(sim >= 0 && sim <= 3, "unknown similarity");
-    OSK_REQUIRE(n_rows <= 0x7FFFFFFFll, "a Lucene segment holds < 2^31 docs");
-    if (ord_to_doc == nullptr) OSK_REQUIRE(max_doc >= n_rows, "max_doc < n_rows for a dense field");
-    int32_t rc = check_device(device);
-    if (rc) return rc;
-    auto s = std::make_unique<osk_seg>();
-    s->device = device;
-    s->n_rows = n_rows;
-    s->dim = dim;
-    s->enc = enc;
-    s->sim = sim;
-    s->max_doc = max_doc;
-    s->units = units_for(dim, enc);
-    s->cfg = cfg_index(s->units);
-    const size_t bytes = (size_t)std::max<int64_t>(1, n_rows) * s->units * 16;
-    hipError_t e = hipMalloc(&s->d_rows, bytes);
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc of segment rows failed: ") + hipGetErrorString(e));
-        return OSK_ERR_OOM;
-    }
-    out = std::move(s);
-    return OSK_OK;
-}
-
-}  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // C-ABI
@@ -392,18 +230,15 @@ int32_t osk_testing_glds_probe(int32_t device, int64_t* out_mismatches) {
     constexpr int kSrc = 1024, kImg = 1024, kCases = 6;
     std::vector<int4> h_src(kSrc), h_out((size_t)kCases * kImg);
     for (int i = 0; i < kSrc; ++i) h_src[i] = make_int4(i, i ^ 0x5A5A, 3 * i + 1, 7);
-    int4 *d_src = nullptr, *d_out = nullptr;
-    OSK_HIP(hipMalloc(&d_src, kSrc * sizeof(int4)));
-    if (hipMalloc(&d_out, h_out.size() * sizeof(int4)) != hipSuccess) {
-        (void)hipFree(d_src);
+    DevBuf d_src, d_out;
+    OSK_HIP(d_src.reserve(kSrc * sizeof(int4)));
+    if (d_out.reserve(h_out.size() * sizeof(int4)) != hipSuccess) {
         set_error("hipMalloc failed");
         return OSK_ERR_DEVICE;
     }
-    hipError_t e = hipMemcpy(d_src, h_src.data(), kSrc * sizeof(int4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_glds_probe(d_src, d_out, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(h_out.data(), d_out, h_out.size() * sizeof(int4), hipMemcpyDeviceToHost);
-    (void)hipFree(d_src);
-    (void)hipFree(d_out);
+    hipError_t e = hipMemcpy(d_src.p, h_src.data(), kSrc * sizeof(int4), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_glds_probe(d_src.as<int4>(), d_out.as<int4>(), nullptr);
+    if (e == hipSuccess) e = hipMemcpy(h_out.data(), d_out.p, h_out.size() * sizeof(int4), hipMemcpyDeviceToHost);
     if (e != hipSuccess) {
         set_error(std::string("glds probe: ") + hipGetErrorString(e));
         return OSK_ERR_DEVICE;
@@ -450,8 +285,8 @@ int32_t osk_seg_stage(int32_t device, const void* rows, int64_t n_rows, int32_t 
     const int64_t src_pitch = (int64_t)dim * elem;
     const int64_t dst_pitch = (int64_t)s->units * 16;
     if (n_rows > 0) {
-        OSK_HIP(hipMemset2DAsync(s->d_rows, dst_pitch, 0, dst_pitch, n_rows, st));
-        OSK_HIP(hipMemcpy2DAsync(s->d_rows, dst_pitch, rows, src_pitch, src_pitch, n_rows,
+        OSK_HIP(hipMemset2DAsync(s->d_rows.p, dst_pitch, 0, dst_pitch, n_rows, st));
+        OSK_HIP(hipMemcpy2DAsync(s->d_rows.p, dst_pitch, rows, src_pitch, src_pitch, n_rows,
                                  hipMemcpyHostToDevice, st));
     }
     rc = seg_finish(s.get(), ord_to_doc, st);
@@ -516,14 +351,14 @@ int32_t osk_seg_stage_file(int32_t device, const char* path, int64_t data_offset
             if ((e = ring[i].reserve((size_t)std::min(n_rows, rows_per) * row_bytes)) != hipSuccess) fail(e, "pinned staging buffer");
             else if ((e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)) != hipSuccess) fail(e, "staging event");
         }
-        if (!err && (e = hipMemset2DAsync(s->d_rows, dst_pitch, 0, dst_pitch, n_rows, st)) != hipSuccess)
+        if (!err && (e = hipMemset2DAsync(s->d_rows.p, dst_pitch, 0, dst_pitch, n_rows, st)) != hipSuccess)
             fail(e, "hipMemset2DAsync");
         int slot = 0;
         for (int64_t r0 = 0; r0 < n_rows && !err; r0 += rows_per, slot ^= 1) {
             const int64_t cnt = std::min(rows_per, n_rows - r0);
             if (used[slot] && (e = hipEventSynchronize(ev[slot])) != hipSuccess) { fail(e, "hipEventSynchronize"); break; }
             std::memcpy(ring[slot].p, src + r0 * row_bytes, (size_t)(cnt * row_bytes));
-            if ((e = hipMemcpy2DAsync(static_cast<char*>(s->d_rows) + r0 * dst_pitch, dst_pitch, ring[slot].p, row_bytes,
+            if ((e = hipMemcpy2DAsync(s->d_rows.as<char>() + r0 * dst_pitch, dst_pitch, ring[slot].p, row_bytes,
                                       row_bytes, cnt, hipMemcpyHostToDevice, st)) != hipSuccess) { fail(e, "hipMemcpy2DAsync"); break; }
             if ((e = hipEventRecord(ev[slot], st)) != hipSuccess) { fail(e, "hipEventRecord"); break; }
             used[slot] = true;
@@ -555,7 +390,7 @@ int32_t osk_seg_stage_device(int32_t device, const void* d_rows, int64_t src_pit
     const int64_t elem = elem_bytes(encoding);
     OSK_REQUIRE(src_pitch_bytes >= (int64_t)dim * elem, "src_pitch_bytes < dim * element size");
     if (n_rows > 0)
-        OSK_HIP(launch_pad_rows(d_rows, src_pitch_bytes, s->d_rows, (int64_t)s->units * 16, n_rows,
+        OSK_HIP(launch_pad_rows(d_rows, src_pitch_bytes, s->d_rows.p, (int64_t)s->units * 16, n_rows,
                                 (int64_t)dim * elem, st));
     rc = seg_finish(s.get(), ord_to_doc, st);
     if (rc) return rc;
@@ -578,7 +413,7 @@ int32_t osk_seg_synth(int32_t device, int64_t n_rows, int32_t dim, int32_t encod
     if (rc) return rc;
     hipStream_t st = device_stream(device);
     if (n_rows > 0)
-        OSK_HIP(launch_synth(s->d_rows, n_rows, dim, s->units, encoding, seed, dist, row0, st));
+        OSK_HIP(launch_synth(s->d_rows.p, n_rows, dim, s->units, encoding, seed, dist, row0, st));
     rc = seg_finish(s.get(), nullptr, st);
     if (rc) return rc;
     *out = s.release();
@@ -796,28 +631,15 @@ int32_t osk_view_create(osk_seg* const* segs, int32_t n_segs, const int32_t* seg
     OSK_REQUIRE(total < 0xFFFFFFFFll, "a view holds < 2^32 rows");
     std::vector<SegDev> sd = seg_devs(v.get());
     hipStream_t st = device_stream(v->device);
-    OSK_HIP(v->d_segs.reserve(sizeof(SegDev) * n_segs));
-    OSK_HIP(v->d_tiles.reserve(sizeof(TileDev) * std::max<size_t>(1, tiles.size())));
-    OSK_HIP(v->d_shard_tile_begin.reserve(sizeof(int32_t) * (n_shards + 1)));
-    OSK_HIP(v->d_shard_index.reserve(sizeof(int32_t) * n_shards));
-    OSK_HIP(v->d_tile_coff.reserve(sizeof(int32_t) * tile_coff.size()));
-    OSK_HIP(v->d_tile_order.reserve(sizeof(int32_t) * tile_order.size()));
-    OSK_HIP(v->d_seg_vrow.reserve(sizeof(int64_t) * n_segs));
     OSK_HIP(v->d_counters.reserve(sizeof(unsigned long long) * kCtrCount));
     OSK_HIP(hipMemsetAsync(v->d_counters.p, 0, sizeof(unsigned long long) * kCtrCount, st));
-    OSK_HIP(hipMemcpyAsync(v->d_seg_vrow.p, vrow.data(), sizeof(int64_t) * n_segs, hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_segs.p, sd.data(), sizeof(SegDev) * n_segs, hipMemcpyHostToDevice, st));
-    if (!tiles.empty())
-        OSK_HIP(hipMemcpyAsync(v->d_tiles.p, tiles.data(), sizeof(TileDev) * tiles.size(),
-                               hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_shard_tile_begin.p, v->shard_tile_begin.data(),
-                           sizeof(int32_t) * (n_shards + 1), hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_shard_index.p, v->shard_index.data(), sizeof(int32_t) * n_shards,
-                           hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_tile_coff.p, tile_coff.data(), sizeof(int32_t) * tile_coff.size(),
-                           hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_tile_order.p, tile_order.data(), sizeof(int32_t) * tile_order.size(),
-                           hipMemcpyHostToDevice, st));
+    OSK_HIP(v->d_seg_vrow.upload(vrow, st));
+    OSK_HIP(v->d_segs.upload(sd, st));
+    OSK_HIP(v->d_tiles.upload(tiles, st));
+    OSK_HIP(v->d_shard_tile_begin.upload(v->shard_tile_begin, st));
+    OSK_HIP(v->d_shard_index.upload(v->shard_index, st));
+    OSK_HIP(v->d_tile_coff.upload(tile_coff, st));
+    OSK_HIP(v->d_tile_order.upload(tile_order, st));
     OSK_HIP(hipStreamSynchronize(st));
     for (osk_seg* sg : v->segs) sg->refs.fetch_add(1);   // released by ~osk_view
     *out = v.release();
@@ -919,15 +741,6 @@ inline hipEvent_t launch_ev_stop(const osk_view* v, int q0, int nq, int chunk = 
     return v->profile && q0 + chunk >= nq ? v->ev1 : nullptr;
 }
 
-// the device's CUs (cached; the persistent kernels' grids and the wide tile table are sized by them)
-int view_cus(osk_view* v) {
-    if (v->n_cus <= 0 &&
-        (hipDeviceGetAttribute(&v->n_cus, hipDeviceAttributeMultiprocessorCount, v->device) != hipSuccess ||
-         v->n_cus <= 0))
-        v->n_cus = 256;
-    return v->n_cus;
-}
-
 // Nothing staged: every shard returns zero hits.
 int32_t zero_shard_hits(const osk_view* v, int nq, int k, uint64_t* d_shard_keys, int32_t* d_shard_counts,
                         int64_t* d_visited, hipStream_t st) {
@@ -967,146 +780,6 @@ int32_t stream_search(osk_view* v, const void* qpad, const void* qnorm, int nq, 
     OSK_HIP(launch_merge_shards(v->ws_cand.as<uint64_t>(), v->n_tiles,
                                 v->d_shard_tile_begin.as<int32_t>(), v->n_shards, nq, k,
                                 d_shard_keys, d_shard_counts, st));
-    return OSK_OK;
-}
-
-// The view's tables of the nested search (caller holds v->mu): every segment's row→parent table and its
-// parent-slot base — segments in the tile table's order (by shard, then segment), so a shard's parent slots
-// are contiguous — and the parent tiles: runs of ≤ kNestPtile slots of one shard.  Built once.
-int32_t ensure_nested(osk_view* v, hipStream_t st) {
-    if (v->nest_ready) return OSK_OK;
-    const int ns = (int)v->segs.size(), S = v->n_shards;
-    std::vector<NestSeg> nsegs(ns);
-    std::vector<NestPtile> ptiles;
-    std::vector<int32_t> spb(S + 1, 0);
-    int64_t slots = 0;
-    for (int sh = 0; sh < S; ++sh) {
-        spb[sh] = (int32_t)ptiles.size();
-        const int64_t first = slots;
-        for (int i = 0; i < ns; ++i) {
-            if (v->seg_shard[i] != sh) continue;
-            osk_seg* sg = v->segs[i];
-            std::lock_guard<std::mutex> lk(sg->mu);
-            OSK_REQUIRE(sg->n_parents > 0 && sg->d_row_parent != nullptr,
-                        "nested search: a segment of the view has no parents registered (osk_seg_set_parents)");
-            nsegs[i] = NestSeg{sg->d_row_parent, slots};
-            slots += sg->n_parents;
-        }
-        for (int64_t b = first; b < slots; b += kNestPtile)
-            ptiles.push_back(NestPtile{b, std::min<int64_t>(b + kNestPtile, slots)});
-    }
-    spb[S] = (int32_t)ptiles.size();
-    OSK_REQUIRE(ptiles.size() < (size_t)(1 << 24), "too many parent tiles");
-    OSK_HIP(v->d_nest_segs.reserve(sizeof(NestSeg) * ns));
-    OSK_HIP(v->d_ptiles.reserve(sizeof(NestPtile) * std::max<size_t>(1, ptiles.size())));
-    OSK_HIP(v->d_shard_ptile_begin.reserve(sizeof(int32_t) * (S + 1)));
-    OSK_HIP(hipMemcpyAsync(v->d_nest_segs.p, nsegs.data(), sizeof(NestSeg) * ns, hipMemcpyHostToDevice, st));
-    if (!ptiles.empty())
-        OSK_HIP(hipMemcpyAsync(v->d_ptiles.p, ptiles.data(), sizeof(NestPtile) * ptiles.size(), hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_shard_ptile_begin.p, spb.data(), sizeof(int32_t) * (S + 1), hipMemcpyHostToDevice, st));
-    OSK_HIP(hipStreamSynchronize(st));   // the sources are locals
-    v->nest_parents = slots;
-    v->n_ptiles = (int)ptiles.size();
-    v->nest_ready = true;
-    return OSK_OK;
-}
-
-// The segment's bf16 hi/lo copy in MFMA fragment order (+ |x|² rows and their max).  Built once.
-int32_t ensure_split(osk_seg* s, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (s->d_split) return OSK_OK;
-    const int KS = ((s->units + 7) / 8 + kKsAlign - 1) / kKsAlign * kKsAlign;   // 32-dim K-steps (padded)
-    const int64_t n_tiles = (s->n_rows + 127) / 128;        // 128-row tiles
-    const int64_t n_rb = std::max<int64_t>(1, n_tiles) * 8;
-    if (!s->d_xnorm_f) {
-        OSK_HIP(hipMalloc(&s->d_xnorm_f, std::max<int64_t>(1, s->n_rows) * sizeof(float)));
-        if (s->n_rows > 0)
-            OSK_HIP(launch_row_norms_f32(static_cast<const float4*>(s->d_rows), s->n_rows, s->units, s->cfg,
-                                         s->d_xnorm_f, st));
-    }
-    void* split = nullptr;
-    hipError_t e = hipMalloc(&split, (size_t)n_rb * KS * 2 * 1024);
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc of the MFMA split copy failed: ") + hipGetErrorString(e));
-        return OSK_ERR_OOM;
-    }
-    OSK_HIP(launch_split_rows(static_cast<const float4*>(s->d_rows), s->n_rows, s->units, KS, n_rb, split, st));
-    OSK_HIP(hipMalloc(&s->d_xsqrt, std::max<int64_t>(1, s->n_rows) * sizeof(float)));
-    if (s->n_rows > 0) OSK_HIP(launch_row_sqrt(s->d_xnorm_f, s->n_rows, s->d_xsqrt, st));
-    OSK_HIP(hipMalloc(&s->d_maxnorm2, sizeof(unsigned)));
-    OSK_HIP(hipMemsetAsync(s->d_maxnorm2, 0, sizeof(unsigned), st));
-    if (s->n_rows > 0) OSK_HIP(launch_max_norm2(s->d_xnorm_f, s->n_rows, s->d_maxnorm2, st));
-    unsigned bits = 0;
-    OSK_HIP(hipMemcpyAsync(&bits, s->d_maxnorm2, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    OSK_HIP(hipStreamSynchronize(st));
-    std::memcpy(&s->h_maxnorm2, &bits, 4);
-    s->d_split = split;
-    s->split_KS = KS;
-    return OSK_OK;
-}
-
-// MFMA work units (runs of 128-row tiles, contiguous per shard) and per-shard bounds.  Built once.
-int32_t ensure_mfma(osk_view* v, hipStream_t st) {
-    if (v->mfma_ready) return OSK_OK;
-    const int ns = (int)v->segs.size();
-    std::vector<const void*> splits(ns);
-    std::vector<const float*> xsq(ns);
-    std::vector<int64_t> vrow(ns);
-    int64_t acc = 0, total_tiles = 0;
-    for (int i = 0; i < ns; ++i) {
-        int32_t rc = ensure_split(v->segs[i], st);
-        if (rc) return rc;
-        splits[i] = v->segs[i]->d_split;
-        xsq[i] = v->segs[i]->d_xsqrt;
-        vrow[i] = acc;
-        acc += v->segs[i]->n_rows;
-        total_tiles += (v->segs[i]->n_rows + 127) / 128;
-    }
-    OSK_REQUIRE(acc < 0xFFFFFFFFll, "a view holds < 2^32 rows");
-    {   // ensure_split may have added row norms: refresh the device segment table
-        const std::vector<SegDev> sd = seg_devs(v);
-        OSK_HIP(hipMemcpyAsync(v->d_segs.p, sd.data(), sizeof(SegDev) * sd.size(), hipMemcpyHostToDevice, st));
-    }
-    // auto: one workgroup per CU (1 per CU fits: 255 VGPRs, 143 KiB LDS) in 1 round below 16k tiles
-    // (C2 b256: 0.74 → 0.65 ms, fewer pilot tiles), else 2 rounds (C3 b256: 11.6 ms against 11.7;
-    // 384 units, 1.5 rounds, lose 30 %; profiles/r02q/mfma_units.txt)
-    const int64_t target = g_tuning.mfma_units > 0 ? (int64_t)g_tuning.mfma_units : (total_tiles < 16384 ? 256 : 512);
-    const int64_t per = std::max<int64_t>(1, (total_tiles + target - 1) / target);
-    std::vector<MfmaUnit> units;
-    std::vector<int32_t> shard_list_begin(v->n_shards + 1, 0);
-    std::vector<float> shard_max(v->n_shards, 0.0f);
-    for (int sh = 0; sh < v->n_shards; ++sh) {
-        shard_list_begin[sh] = (int32_t)units.size() * 2;
-        for (int i = 0; i < ns; ++i) {
-            if (v->seg_shard[i] != sh) continue;
-            shard_max[sh] = std::max(shard_max[sh], v->segs[i]->h_maxnorm2);
-            const int64_t nt = (v->segs[i]->n_rows + 127) / 128;
-            for (int64_t t = 0; t < nt; t += per)
-                units.push_back(MfmaUnit{i, sh, t, std::min(nt, t + per), vrow[i]});
-        }
-    }
-    shard_list_begin[v->n_shards] = (int32_t)units.size() * 2;
-    v->n_munits = (int)units.size();
-    OSK_REQUIRE(v->n_munits > 0 && v->n_munits < 65536, "bad MFMA unit count");
-    v->mfma_KS = ((v->units + 7) / 8 + kKsAlign - 1) / kKsAlign * kKsAlign;
-    // |Σ approx − Σ device order| ≤ c·|x||q|: bf16 split (3·2^-16) + fp32 accumulation of the
-    // 3·Kpad MFMA products and of the Kpad device-order products (γ_n ≈ n·2^-24), ×1.5 margin.
-    const double kpad = 32.0 * v->mfma_KS;
-    v->mfma_c = 1.5 * (3.0 * std::ldexp(1.0, -16) + 4.0 * kpad * std::ldexp(1.0, -24));
-    OSK_HIP(v->d_munits.reserve(sizeof(MfmaUnit) * units.size()));
-    OSK_HIP(v->d_seg_split.reserve(sizeof(void*) * ns));
-    OSK_HIP(v->d_seg_xsqrt.reserve(sizeof(void*) * ns));
-    OSK_HIP(v->d_shard_unit_begin.reserve(sizeof(int32_t) * (v->n_shards + 1)));
-    OSK_HIP(v->d_shard_maxnorm2.reserve(sizeof(float) * v->n_shards));
-    OSK_HIP(hipMemcpyAsync(v->d_munits.p, units.data(), sizeof(MfmaUnit) * units.size(), hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_seg_split.p, splits.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_seg_xsqrt.p, xsq.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_shard_unit_begin.p, shard_list_begin.data(), sizeof(int32_t) * (v->n_shards + 1),
-                           hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_shard_maxnorm2.p, shard_max.data(), sizeof(float) * v->n_shards,
-                           hipMemcpyHostToDevice, st));
-    OSK_HIP(hipStreamSynchronize(st));
-    v->mfma_ready = true;
     return OSK_OK;
 }
 
@@ -1224,347 +897,6 @@ int32_t batched_search(osk_view* v, int nq, int k, int UP, const uint64_t* const
     return OSK_OK;
 }
 
-// The segment's int8 copy + per-row bound terms for the certified prefilter.  Built once.
-int32_t ensure_sq8_seg(osk_seg* s, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (s->d_q8) return OSK_OK;
-    const int u8 = (s->dim + 15) / 16;
-    void* q8 = nullptr;
-    hipError_t e = hipMalloc(&q8, (size_t)std::max<int64_t>(1, s->n_rows) * u8 * 16);
-    if (e != hipSuccess) {
-        set_error(std::string("hipMalloc of the int8 prefilter copy failed: ") + hipGetErrorString(e));
-        return OSK_ERR_OOM;
-    }
-    float4* aux = nullptr;
-    e = hipMalloc(&aux, (size_t)std::max<int64_t>(1, s->n_rows) * sizeof(float4));
-    if (e != hipSuccess) {
-        (void)hipFree(q8);
-        set_error(std::string("hipMalloc of the prefilter bound terms failed: ") + hipGetErrorString(e));
-        return OSK_ERR_OOM;
-    }
-    // (the kernel also reports whether some row lies outside the certificate's range: one int, read below)
-    int* d_oor = nullptr;
-    OSK_HIP(hipMalloc(reinterpret_cast<void**>(&d_oor), sizeof(int)));
-    OSK_HIP(hipMemsetAsync(d_oor, 0, sizeof(int), st));
-    OSK_HIP(launch_sq8_quantize(static_cast<const float4*>(s->d_rows), s->n_rows, s->units, s->units, u8, q8, aux,
-                                0, st, d_oor));
-    // the 6-bit tier of single queries, where the dim has one and the tier is on (a node
-    // that sets tune sq6 = 0 before staging never holds the copy; calibration frees it per segment)
-    void* q6 = nullptr;
-    float4* aux6 = nullptr;
-    if (sq6_supported(s->dim) && g_tuning.sq6.load(std::memory_order_relaxed)) {
-        // (stream-ordered allocations: the calibration frees them with hipFreeAsync behind the events of the
-        // launches that read them, no device-wide wait — fold_probe)
-        const int64_t b6 = sq6_bytes(s->n_rows, s->dim), ba = std::max<int64_t>(1, s->n_rows) * 16;
-        e = hipMallocAsync(&q6, (size_t)(b6 - ba), st);
-        if (e == hipSuccess) e = hipMallocAsync(reinterpret_cast<void**>(&aux6), (size_t)ba, st);
-        if (e != hipSuccess) {
-            if (q6) (void)hipFreeAsync(q6, st);
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(q8);
-            (void)hipFree(aux);
-            set_error(std::string("hipMalloc of the 6-bit prefilter tier failed: ") + hipGetErrorString(e));
-            return OSK_ERR_OOM;
-        }
-        OSK_HIP(launch_sq6_quantize(static_cast<const float4*>(s->d_rows), s->n_rows, s->units, s->dim, q6, aux6, st));
-    }
-    OSK_HIP(hipStreamSynchronize(st));
-    int oor = 0;
-    OSK_HIP(hipMemcpy(&oor, d_oor, sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipFree(d_oor);
-    s->sq8_out_of_range = oor != 0;
-    s->d_q8 = q8;
-    s->d_q8aux = aux;
-    s->d_q6 = q6;
-    s->d_q6aux = aux6;
-    s->units8 = u8;
-    return OSK_OK;
-}
-
-// The segment's int8 copy in sq8_mfma's tiled layout: blocks of 16 rows, per 64-dim k-step one
-// contiguous 1 KiB slab (chunk-major: 16-dim chunk c of row r at c·256 + r·16 B), so each of the scan's
-// load instructions reads 1 KiB contiguous and a 32-dim tail is the slab's first 512 B.  Built once, from
-// the row-major int8 copy.
-int32_t ensure_sq8t_seg(osk_seg* s, hipStream_t st, bool wide) {
-    std::lock_guard<std::mutex> lk(s->mu);
-    const int u8 = (s->dim + 15) / 16;
-    const int64_t blocks = std::max<int64_t>(1, (s->n_rows + 15) / 16);
-    if (!s->d_q8t) {
-        const int ks = sq8_mfma_ks(u8);
-        void* q8t = nullptr;
-        hipError_t e = hipMalloc(&q8t, (size_t)blocks * ks * 1024);
-        if (e != hipSuccess) {
-            set_error(std::string("hipMalloc of the tiled int8 copy failed: ") + hipGetErrorString(e));
-            return OSK_ERR_OOM;
-        }
-        OSK_HIP(launch_sq8_tile(s->d_q8, s->n_rows, u8, ks, q8t, st));
-        OSK_HIP(hipStreamSynchronize(st));
-        s->d_q8t = q8t;
-    }
-    // the wide kernel's own copy (osk_sq8w.hip launch_sq8w_build): codes with one scale per 16-row group,
-    // tiled, and their bound terms per group (352 B per 16 rows).  Built the first time the cost model sends a
-    // batch of this segment's view to the wide kernel (a node whose batches never take it does not
-    // hold a second int8 copy — at 768 dims +768 B per row)
-    if (wide && !s->d_q8w && sq8_wide_supported(u8)) {
-        void* q8w = nullptr;
-        float4* auxt = nullptr;
-        hipError_t e = hipMalloc(&q8w, (size_t)blocks * sq8_wide_ks(u8) * 1024);
-        if (e == hipSuccess) e = hipMalloc(&auxt, (size_t)blocks * kAuxGroupF4 * sizeof(float4));
-        if (e != hipSuccess) {
-            if (q8w) (void)hipFree(q8w);
-            set_error(std::string("hipMalloc of the wide prefilter copy failed: ") + hipGetErrorString(e));
-            return OSK_ERR_OOM;
-        }
-        OSK_HIP(launch_sq8w_build(static_cast<const float4*>(s->d_rows), s->n_rows, s->units, u8,
-                                  s->sim == SIM_COSINE ? s->d_xnorm_f : nullptr, s->sim == SIM_COSINE ? 1 : 0, q8w, auxt,
-                                  st));
-        OSK_HIP(hipStreamSynchronize(st));
-        s->d_q8w = q8w;
-        s->d_q8auxt = auxt;
-    }
-    return OSK_OK;
-}
-
-int32_t ensure_sq8t(osk_view* v, hipStream_t st) {
-    if (v->sq8t_ready) return OSK_OK;
-    const int ns = (int)v->segs.size();
-    std::vector<const void*> rows(ns);
-    for (int i = 0; i < ns; ++i) {
-        int32_t rc = ensure_sq8t_seg(v->segs[i], st, false);
-        if (rc) return rc;
-        rows[i] = v->segs[i]->d_q8t;
-    }
-    OSK_HIP(v->d_sq8_rows_t.reserve(sizeof(void*) * ns));
-    OSK_HIP(hipMemcpyAsync(v->d_sq8_rows_t.p, rows.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-    OSK_HIP(hipStreamSynchronize(st));
-    v->sq8t_ready = true;
-    return OSK_OK;
-}
-
-// The wide kernel's inputs for a view (first batch the cost model sends to it): every segment's group-scaled
-// copy and tiled bound terms, and the view's own tile table of quarters.
-int32_t ensure_sq8w(osk_view* v, hipStream_t st) {
-    if (v->sq8w_ready) return OSK_OK;
-    int32_t rc = ensure_sq8t(v, st);
-    if (rc) return rc;
-    const int ns = (int)v->segs.size();
-    std::vector<const void*> rows_w(ns), auxt(ns);
-    for (int i = 0; i < ns; ++i) {
-        rc = ensure_sq8t_seg(v->segs[i], st, true);
-        if (rc) return rc;
-        rows_w[i] = v->segs[i]->d_q8w;
-        auxt[i] = v->segs[i]->d_q8auxt;
-    }
-    OSK_HIP(v->d_sq8_rows_w.reserve(sizeof(void*) * ns));
-    OSK_HIP(v->d_sq8_auxt.reserve(sizeof(void*) * ns));
-    OSK_HIP(hipMemcpyAsync(v->d_sq8_rows_w.p, rows_w.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_sq8_auxt.p, auxt.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-    if (sq8_wide_supported((v->segs.empty() ? 0 : v->segs[0]->units8)) && v->n_tiles > 0) {
-        // The wide kernel's own tiles: its lists are per (tile, quarter) and every quarter's lists are
-        // written for all 256 queries, so quarters of the scan tiles (≈ 244 rows at C2) would make the list
-        // traffic rival the corpus.  Quarters here hold ≈ R / (2·CUs) rows, 256 … 16,384 (C2 ≈ 2k, C4 16k;
-        // two to a few dozen per persistent workgroup), tiles never span segments, cut at multiples of 16.
-        const int cus = view_cus(v);
-        double R = 0.0;
-        for (const osk_seg* sg : v->segs) R += (double)sg->n_rows;
-        // (≥ 512 dims: quarters of R / (8·CUs), so the first pass — one round of the persistent grid — covers
-        // 1/8 of the rows, not 1/2, and the second pass's floors come early; list traffic is small beside
-        // rows of ≥ 512 B)
-        const int u8w = v->segs.empty() ? 1 : v->segs[0]->units8;
-        const int qdiv = sq8_wide_ks(u8w) >= 8 ? 8 : 2;
-        // (≤ 16,384 rows, round 5's best for the ring kernel; the rows kernel ran C4 b1024 in 16.05 ms at 32,768
-        // against 16.42 (profiles/r06/tune14.jsonl) but a first-pass quarter that long can fill a queue: one C4
-        // query in 256 took an exact re-scan, profiles/r06/rows_clocks_c4_b256_q32768.log)
-        const int64_t qmax = 16384;
-        const int64_t qr = g_tuning.sq8_wide_quarter_rows > 0
-                               ? std::max<int64_t>(16, (int64_t)g_tuning.sq8_wide_quarter_rows & ~15ll)
-                               : std::min<int64_t>(qmax, std::max<int64_t>(256, (int64_t)(R / ((double)qdiv * cus)) + 15 & ~15ll));
-        const int64_t trows = 4 * qr;
-        std::vector<TileDev> wt;
-        v->wshard_tile_begin.assign(v->n_shards + 1, 0);
-        for (int sh = 0; sh < v->n_shards; ++sh) {
-            v->wshard_tile_begin[sh] = (int32_t)wt.size();
-            for (int i = 0; i < ns; ++i) {
-                if ((v->seg_shard.empty() ? 0 : v->seg_shard[i]) != sh) continue;
-                const int64_t n = v->segs[i]->n_rows;
-                if (n == 0) continue;
-                const int64_t nt = (n + trows - 1) / trows;
-                auto cut = [&](int64_t t) { return t >= nt ? n : (n * t / nt) & ~(int64_t)15; };
-                for (int64_t t = 0; t < nt; ++t)
-                    if (cut(t + 1) > cut(t)) wt.push_back(TileDev{i, sh, cut(t), cut(t + 1)});
-            }
-        }
-        v->wshard_tile_begin[v->n_shards] = (int32_t)wt.size();
-        v->n_wtiles = (int)wt.size();
-        std::vector<int32_t> order(std::max<size_t>(1, wt.size()), 0), sqb(v->n_shards + 1);
-        {   // interleaved over shards (as the scan tiles' order)
-            std::vector<std::pair<double, int>> key;
-            for (int sh = 0; sh < v->n_shards; ++sh) {
-                const int t0 = v->wshard_tile_begin[sh], n = v->wshard_tile_begin[sh + 1] - t0;
-                for (int j = 0; j < n; ++j) key.push_back({(j + 0.5) / n, t0 + j});
-            }
-            std::stable_sort(key.begin(), key.end(), [](auto& a, auto& b) { return a.first < b.first; });
-            for (size_t i = 0; i < key.size(); ++i) order[i] = key[i].second;
-        }
-        for (int i = 0; i <= v->n_shards; ++i) sqb[i] = 4 * v->wshard_tile_begin[i];
-        OSK_HIP(v->d_wtiles.reserve(sizeof(TileDev) * std::max<size_t>(1, wt.size())));
-        OSK_HIP(v->d_wtile_order.reserve(sizeof(int32_t) * order.size()));
-        OSK_HIP(v->d_wshard_tile_begin.reserve(sizeof(int32_t) * (v->n_shards + 1)));
-        OSK_HIP(v->d_shard_quarter_begin.reserve(sizeof(int32_t) * sqb.size()));
-        if (!wt.empty())
-            OSK_HIP(hipMemcpyAsync(v->d_wtiles.p, wt.data(), sizeof(TileDev) * wt.size(), hipMemcpyHostToDevice, st));
-        OSK_HIP(hipMemcpyAsync(v->d_wtile_order.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, st));
-        OSK_HIP(hipMemcpyAsync(v->d_wshard_tile_begin.p, v->wshard_tile_begin.data(), sizeof(int32_t) * (v->n_shards + 1),
-                               hipMemcpyHostToDevice, st));
-        OSK_HIP(hipMemcpyAsync(v->d_shard_quarter_begin.p, sqb.data(), sizeof(int32_t) * sqb.size(), hipMemcpyHostToDevice,
-                               st));
-        OSK_HIP(v->d_quarter_bm.reserve(sizeof(float4) * 4 * std::max<size_t>(1, wt.size())));
-        OSK_HIP(launch_wide_quarter_max(v->d_wtiles.as<TileDev>(), v->n_wtiles, v->d_sq8_auxt.as<const float4*>(),
-                                        v->d_quarter_bm.as<float4>(), st));
-        // the quarters' descriptors, read by every workgroup's setup instead of recomputed (64 B each)
-        OSK_HIP(v->d_wqtable.reserve((size_t)64 * 4 * std::max<size_t>(1, wt.size())));
-        OSK_HIP(launch_wide_quarter_table(v->d_wtiles.as<TileDev>(), v->d_wtile_order.as<int32_t>(), 4 * v->n_wtiles,
-                                          sq8_wide_ks(u8w), v->d_sq8_rows_w.p, v->d_sq8_auxt.p,
-                                          v->d_seg_vrow.as<int64_t>(), v->d_quarter_bm.as<const float4>(),
-                                          v->d_wqtable.p, st));
-    }
-    OSK_HIP(hipStreamSynchronize(st));
-    v->sq8w_ready = true;
-    return OSK_OK;
-}
-
-// Settle slices over the wave lists of a tile table (list = tile·4 + wave): kSliceLists lists each,
-// never spanning shards (an empty shard gets one empty slice so its result is still written); each
-// slice carries its L group (aligned chunks of kLGroupLists lists of the shard).
-void settle_slices(const std::vector<int32_t>& shard_tile_begin, std::vector<int4>& sl, std::vector<int32_t>& ssb) {
-    const int S = (int)shard_tile_begin.size() - 1;
-    sl.clear();
-    ssb.assign(S + 1, 0);
-    for (int sh = 0; sh < S; ++sh) {
-        ssb[sh] = (int32_t)sl.size();
-        const int l0 = 4 * shard_tile_begin[sh], l1 = 4 * shard_tile_begin[sh + 1];
-        if (l0 == l1) sl.push_back(make_int4(l0, l0, l0, l0));
-        for (int l = l0; l < l1; l += kSliceLists) {
-            const int ga = l0 + (l - l0) / kLGroupLists * kLGroupLists;
-            sl.push_back(make_int4(l, std::min(l + kSliceLists, l1), ga, std::min(ga + kLGroupLists, l1)));
-        }
-    }
-    ssb[S] = (int32_t)sl.size();
-}
-
-// Gather tiles for filtered scans over the compacted accepted ordinals (osk_filter.hip): one round of
-// the chip's resident scan workgroups (CUs × 4) split over the segments by rows, at least one per
-// non-empty segment, ordered by shard like the row tiles (so lists never span shards); gather tile
-// j of nj of a segment covers ordinals [cnt·j/nj, cnt·(j+1)/nj) of its cnt accepted ones.  Built once.
-int32_t ensure_gather(osk_view* v, hipStream_t st) {
-    if (v->gather_ready) return OSK_OK;
-    const int ns = (int)v->segs.size();
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v->device) != hipSuccess || cus <= 0)
-        cus = 256;
-    const int64_t target = std::min<int64_t>((int64_t)cus * 4, std::max(1, v->n_tiles));
-    int64_t total = 0;
-    for (osk_seg* sg : v->segs) total += sg->n_rows;
-    std::vector<int4> gt;
-    std::vector<int32_t> gsb(v->n_shards + 1, 0);
-    for (int sh = 0; sh < v->n_shards; ++sh) {
-        gsb[sh] = (int32_t)gt.size();
-        for (int i = 0; i < ns; ++i) {
-            if (v->seg_shard[i] != sh || v->segs[i]->n_rows == 0) continue;
-            const int64_t nj = std::max<int64_t>(1, (int64_t)((double)v->segs[i]->n_rows * target / std::max<int64_t>(1, total)));
-            for (int64_t j = 0; j < nj; ++j) gt.push_back(make_int4(i, sh, (int)j, (int)nj));
-        }
-    }
-    gsb[v->n_shards] = (int32_t)gt.size();
-    std::vector<int4> sl;
-    std::vector<int32_t> ssb;
-    settle_slices(gsb, sl, ssb);
-    // each segment's tile range in the row-tile table (tiles of a segment are contiguous)
-    std::vector<TileDev> tiles(v->n_tiles);
-    if (v->n_tiles)
-        OSK_HIP(hipMemcpyAsync(tiles.data(), v->d_tiles.p, sizeof(TileDev) * v->n_tiles, hipMemcpyDeviceToHost, st));
-    OSK_HIP(hipStreamSynchronize(st));
-    std::vector<int2> seg_tiles(ns, make_int2(0, 0));
-    for (int t = 0; t < v->n_tiles; ++t) {
-        int2& r = seg_tiles[tiles[t].seg];
-        if (r.x == r.y) r = make_int2(t, t + 1);
-        else r.y = t + 1;
-    }
-    v->n_gtiles = (int)gt.size();
-    v->n_gslices = (int)sl.size();
-    OSK_HIP(v->d_gtiles.reserve(sizeof(int4) * std::max<size_t>(1, gt.size())));
-    OSK_HIP(v->d_gslices.reserve(sizeof(int4) * sl.size()));
-    OSK_HIP(v->d_gshard_slice_begin.reserve(sizeof(int32_t) * ssb.size()));
-    OSK_HIP(v->d_seg_tiles.reserve(sizeof(int2) * ns));
-    OSK_HIP(v->ws_tcnt.reserve(sizeof(int32_t) * std::max(1, v->n_tiles)));
-    OSK_HIP(v->ws_scnt.reserve(sizeof(int32_t) * ns));
-    OSK_HIP(v->ws_comp.reserve(sizeof(uint32_t) * std::max<int64_t>(1, total)));
-    if (!gt.empty())
-        OSK_HIP(hipMemcpyAsync(v->d_gtiles.p, gt.data(), sizeof(int4) * gt.size(), hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_gslices.p, sl.data(), sizeof(int4) * sl.size(), hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_gshard_slice_begin.p, ssb.data(), sizeof(int32_t) * ssb.size(), hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_seg_tiles.p, seg_tiles.data(), sizeof(int2) * ns, hipMemcpyHostToDevice, st));
-    OSK_HIP(hipStreamSynchronize(st));
-    v->gather_ready = true;
-    return OSK_OK;
-}
-
-int32_t ensure_sq8(osk_view* v, hipStream_t st) {
-    if (v->sq8_ready) return OSK_OK;
-    const int ns = (int)v->segs.size();
-    std::vector<const void*> rows(ns);
-    std::vector<const float4*> aux(ns);
-    for (int i = 0; i < ns; ++i) {
-        int32_t rc = ensure_sq8_seg(v->segs[i], st);
-        if (rc) return rc;
-        rows[i] = v->segs[i]->d_q8;
-        aux[i] = v->segs[i]->d_q8aux;
-    }
-    v->units8 = (v->dim + 15) / 16;
-    {
-        std::vector<int4> sl;
-        std::vector<int32_t> ssb;
-        settle_slices(v->shard_tile_begin, sl, ssb);
-        v->n_slices = (int)sl.size();
-        OSK_HIP(v->d_slices.reserve(sizeof(int4) * sl.size()));
-        OSK_HIP(v->d_shard_slice_begin.reserve(sizeof(int32_t) * ssb.size()));
-        OSK_HIP(hipMemcpyAsync(v->d_slices.p, sl.data(), sizeof(int4) * sl.size(), hipMemcpyHostToDevice, st));
-        OSK_HIP(hipMemcpyAsync(v->d_shard_slice_begin.p, ssb.data(), sizeof(int32_t) * ssb.size(),
-                               hipMemcpyHostToDevice, st));
-    }
-    // rounding bounds of the fp32 device order over n = 4·units products: γ_n ≤ n·2^-24
-    // (any summation tree); gam = γ_n/2 with a 2× margin, g2 ≥ γ_{n+2} with margin.
-    const double n = 4.0 * v->units;
-    v->sq8_gam = (float)((n + 8.0) * std::ldexp(1.0, -24));
-    v->sq8_g2 = (float)((n + 8.0) * std::ldexp(1.0, -23));
-    v->sq8_cos_slack = (float)((n + 8.0) * std::ldexp(1.0, -23) + std::ldexp(1.0, -18));
-    OSK_HIP(v->d_sq8_rows.reserve(sizeof(void*) * ns));
-    OSK_HIP(v->d_sq8_aux.reserve(sizeof(void*) * ns));
-    OSK_HIP(hipMemcpyAsync(v->d_sq8_rows.p, rows.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-    OSK_HIP(hipMemcpyAsync(v->d_sq8_aux.p, aux.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-    // the 6-bit tier: used only when every segment has one
-    std::vector<const void*> rows6(ns);
-    std::vector<const float4*> aux6(ns);
-    bool all6 = ns > 0;
-    for (int i = 0; i < ns; ++i) {
-        rows6[i] = v->segs[i]->d_q6;
-        aux6[i] = v->segs[i]->d_q6aux;
-        all6 = all6 && rows6[i] && aux6[i];
-    }
-    if (all6) {
-        OSK_HIP(v->d_sq6_rows.reserve(sizeof(void*) * ns));
-        OSK_HIP(v->d_sq6_aux.reserve(sizeof(void*) * ns));
-        OSK_HIP(hipMemcpyAsync(v->d_sq6_rows.p, rows6.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-        OSK_HIP(hipMemcpyAsync(v->d_sq6_aux.p, aux6.data(), sizeof(void*) * ns, hipMemcpyHostToDevice, st));
-    }
-    OSK_HIP(hipStreamSynchronize(st));
-    v->sq6_ready = all6;
-    v->sq8_range_ok = true;
-    for (const osk_seg* sg : v->segs) v->sq8_range_ok = v->sq8_range_ok && !sg->sq8_out_of_range;
-    v->sq8_ready = true;
-    return OSK_OK;
-}
-
 // The 6-bit tier's calibration, folded without waiting: when this view's last probe has
 // landed (its event completed), its per-segment int8 re-bound counts join the segments' calibration; a
 // segment with kSq6Probes probes keeps the tier, or turns it off (re-bounds above sq6_probe_pct % of the
@@ -1598,13 +930,17 @@ void sq6_prune_locked() {
     g_sq6_inflight.resize(j);
 }
 
-// A segment being destroyed leaves the in-flight records (its launches have completed: the destructor's hipFree
-// calls synchronise the device), so a segment later allocated at the same address never waits on them.
-void sq6_forget_segment(const osk_seg* sg) {
+}  // namespace
+
+// A segment being destroyed leaves the in-flight records (its launches have completed: the destructor waits for
+// the device before it calls this), so a segment later allocated at the same address never waits on them.
+void osk::sq6_forget_segment(const osk_seg* sg) {
     std::lock_guard<std::mutex> lk(g_sq6_inflight_mu);
     for (Sq6Inflight& f : g_sq6_inflight) f.segs.erase(std::remove(f.segs.begin(), f.segs.end(), sg), f.segs.end());
     sq6_prune_locked();
 }
+
+namespace {
 
 // A 6-bit launch over a view with a probing segment: record its completion (caller holds the shared side
 // of g_sq6_free_mu, and the view's device is current).
@@ -1801,9 +1137,11 @@ void sq6_share_withdraw(Sq6Group* grp, int slot) {
     (void)hipStreamSynchronize(nullptr);
 }
 
+}  // namespace
+
 // Leave the group: after its last scan has completed the view's query is withdrawn; the group goes with its
 // last view.
-void sq6_share_detach(osk_view* v) {
+void osk::sq6_share_detach(osk_view* v) {
     Sq6Group* grp = static_cast<Sq6Group*>(v->share_group);
     if (!grp) return;
     int cur = -1;
@@ -1834,6 +1172,8 @@ void sq6_share_detach(osk_view* v) {
     }
     if (cur >= 0) (void)hipSetDevice(cur);
 }
+
+namespace {
 
 // ---- Certified int8 prefilter search (float32, k ≤ kKQ): int8 scan → settle per slice of tiles (exact
 // re-score of the rows the certificate cannot exclude; a tile whose list overflowed is re-scanned
@@ -2987,31 +2327,29 @@ int32_t osk_seg_set_parents(osk_seg* seg, const uint64_t* parent_bits) {
     hipStream_t st = device_stream(seg->device);
     int32_t last_doc = -1;   // the last vector's doc
     if (seg->n_rows > 0) {
-        if (seg->d_ord_to_doc)
-            OSK_HIP(hipMemcpy(&last_doc, seg->d_ord_to_doc + (seg->n_rows - 1), sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (seg->d_ord_to_doc.p)
+            OSK_HIP(hipMemcpy(&last_doc, seg->d_ord_to_doc.as<int32_t>() + (seg->n_rows - 1), sizeof(int32_t),
+                              hipMemcpyDeviceToHost));
         else
             last_doc = (int32_t)(seg->n_rows - 1);
     }
     OSK_REQUIRE((int64_t)last_doc <= last, "a vector's doc lies after the last parent doc");
-    int32_t* rp = nullptr;
-    OSK_HIP(hipMalloc(&rp, std::max<int64_t>(1, seg->n_rows) * sizeof(int32_t)));
+    DevBuf rp;
+    OSK_HIP(rp.reserve(std::max<int64_t>(1, seg->n_rows) * sizeof(int32_t)));
     if (seg->n_rows > 0) {
         DevBuf d_bits, d_rank;
-        hipError_t e = d_bits.reserve(bits.size() * 8);
-        if (e == hipSuccess) e = d_rank.reserve(rank.size() * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_bits.p, bits.data(), bits.size() * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rank.p, rank.data(), rank.size() * 4, hipMemcpyHostToDevice, st);
+        hipError_t e = d_bits.upload(bits, st);
+        if (e == hipSuccess) e = d_rank.upload(rank, st);
         if (e == hipSuccess)
-            e = launch_nest_parents(d_bits.as<uint64_t>(), d_rank.as<int32_t>(), n_words, seg->d_ord_to_doc,
-                                    seg->n_rows, rp, st);
+            e = launch_nest_parents(d_bits.as<uint64_t>(), d_rank.as<int32_t>(), n_words,
+                                    seg->d_ord_to_doc.as<int32_t>(), seg->n_rows, rp.as<int32_t>(), st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);   // (the temporaries are freed on return)
         if (e != hipSuccess) {
-            (void)hipFree(rp);
             set_error(std::string("osk_seg_set_parents: ") + hipGetErrorString(e));
             return OSK_ERR_DEVICE;
         }
     }
-    seg->d_row_parent = rp;
+    seg->d_row_parent = std::move(rp);
     seg->n_parents = total;
     return OSK_OK;
     OSK_GUARD_END

@@ -1,5 +1,6 @@
 // osk_objects.h — the host-side object model of libosknn (osk_seg, osk_view, osk_comm helpers) shared
-// by the C-ABI translation units (osk_api.hip, osk_comm.hip).  Not part of the public ABI.
+// by the C-ABI translation units (osk_api.hip, osk_comm.hip) and the lifetime and builder code
+// (osk_derived.hip).  Not part of the public ABI.
 //
 //   osk_seg   one segment's vector field in HBM (rows padded to 16-byte units, optional row norms,
 //             optional ord→doc map, and the derived copies the fast paths read: the int8 prefilter
@@ -13,6 +14,7 @@
 //             S/search/internal/ContextIndexSearcher.java:203-218).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -74,18 +76,39 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) {
+        o.p = nullptr;
+        o.cap = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p;
+            cap = o.cap;
+            o.p = nullptr;
+            o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
         if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
     }
     hipError_t reserve(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
-        if (p) {
-            (void)hipFree(p);
-            p = nullptr;
-            cap = 0;
-        }
+        reset();
         hipError_t e = hipMalloc(&p, bytes);
         if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    // A host table onto the device, on `st` (at least one element is reserved).  Does not synchronise: the
+    // caller waits for the stream before `h` goes away.
+    template <class T> hipError_t upload(const std::vector<T>& h, hipStream_t st) {
+        hipError_t e = reserve(sizeof(T) * std::max<size_t>(1, h.size()));
+        if (e == hipSuccess && !h.empty())
+            e = hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, st);
         return e;
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
@@ -127,24 +150,25 @@ struct osk_seg {
     int64_t n_rows = 0;
     int dim = 0, enc = 0, sim = 0, max_doc = 0;
     int units = 0, cfg = 0;
-    void* d_rows = nullptr;
-    float* d_xnorm_f = nullptr;
-    int32_t* d_xnorm_i = nullptr;
-    int32_t* d_ord_to_doc = nullptr;
+    // device memory: each buffer is reserved once, at its exact size (hbm_bytes is the sum of the capacities)
+    osk::DevBuf d_rows;
+    osk::DevBuf d_xnorm_f;             // float |x|² per row (cosine; added by ensure_split otherwise)
+    osk::DevBuf d_xnorm_i;             // int32 |x|² per row (byte fields)
+    osk::DevBuf d_ord_to_doc;          // int32 per row (sparse fields)
     // batched MFMA path (built by osk_seg_warm or on first batched search): bf16 hi/lo copy in MFMA
     // fragment order, |x|² per row (device lane order) and max |x|² of the segment
-    void* d_split = nullptr;
+    osk::DevBuf d_split;
     int split_KS = 0;
-    unsigned* d_maxnorm2 = nullptr;
-    float* d_xsqrt = nullptr;          // |x| per row (MFMA path)
+    osk::DevBuf d_maxnorm2;            // [1] unsigned: the bits of max |x|²
+    osk::DevBuf d_xsqrt;               // float |x| per row (MFMA path)
     float h_maxnorm2 = 0.0f;
     // certified int8 prefilter (built at staging for float32 segments): int8 rows + per-row bound terms
-    void* d_q8 = nullptr;
-    float4* d_q8aux = nullptr;
+    osk::DevBuf d_q8;
+    osk::DevBuf d_q8aux;               // float4 per row
     bool sq8_out_of_range = false;   // some row lies outside the certificate's range (sq8_in_range; set with d_q8)
-    void* d_q8t = nullptr;    // the int8 rows in sq8_mfma's tiled layout (osk_seg_warm / first batched prefilter)
-    void* d_q8w = nullptr;        // sq8_wide's copy: codes with one scale per 16-row group, tiled (launch_sq8w_build)
-    float4* d_q8auxt = nullptr;   // ...and its bound terms per 16-row group (built with d_q8t)
+    osk::DevBuf d_q8t;        // the int8 rows in sq8_mfma's tiled layout (osk_seg_warm / first batched prefilter)
+    osk::DevBuf d_q8w;            // sq8_wide's copy: codes with one scale per 16-row group, tiled (launch_sq8w_build)
+    osk::DevBuf d_q8auxt;         // ...and its float4 bound terms per 16-row group (built with d_q8w)
     void* d_q6 = nullptr;     // the 6-bit tier (dims with sq6_supported, tune sq6 on at staging): tiled codes,
     float4* d_q6aux = nullptr;   // built with the int8 copy; freed when the segment's calibration turns it off
     // The 6-bit tier's calibration, per segment: every view over the segment (a searcher's view, its
@@ -157,7 +181,7 @@ struct osk_seg {
     int units8 = 0;
     // nested k-NN (osk_seg_set_parents, once per segment): each row's parent rank among the leaf's parent
     // docs ([L] the BitSetProducer of the nested path), and their number; guarded by mu
-    int32_t* d_row_parent = nullptr;
+    osk::DevBuf d_row_parent;          // int32 per row
     int64_t n_parents = 0;
     std::mutex mu;
     std::atomic<int> refs{1};          // the reader's reference + one per view that groups the segment
@@ -310,6 +334,44 @@ struct osk_view {
 namespace osk {
 // Drop one reference of a segment (deletes it at zero).
 void seg_unref(osk_seg* s);
+
+// ---- lifetime and built-once structures (osk_derived.hip)
+// The device view of a view's segments (pointers re-read: staging may add row norms later).
+std::vector<SegDev> seg_devs(const osk_view* v);
+// A new segment with its padded rows allocated (arguments checked; the device made current).
+int32_t seg_alloc(int device, int64_t n_rows, int dim, int enc, int sim, int max_doc, const int32_t* ord_to_doc,
+                  std::unique_ptr<osk_seg>& out);
+// The rest of staging once the rows are on the device: row norms, ord→doc map, the int8 prefilter copy.
+int32_t seg_finish(osk_seg* s, const int32_t* ord_to_doc, hipStream_t st);
+// The segment's bf16 hi/lo copy in MFMA fragment order (+ |x|² rows and their max).  Built once.
+int32_t ensure_split(osk_seg* s, hipStream_t st);
+// MFMA work units (runs of 128-row tiles, contiguous per shard) and per-shard bounds.  Built once.
+int32_t ensure_mfma(osk_view* v, hipStream_t st);
+// The view's tables of the nested search (caller holds v->mu).  Built once.
+int32_t ensure_nested(osk_view* v, hipStream_t st);
+// The segment's int8 copy + per-row bound terms for the certified prefilter.  Built once.
+int32_t ensure_sq8_seg(osk_seg* s, hipStream_t st);
+// The segment's int8 copy in sq8_mfma's tiled layout and (wide) the wide kernel's group-scaled copy.  Built once.
+int32_t ensure_sq8t_seg(osk_seg* s, hipStream_t st, bool wide);
+// The view's table of its segments' tiled int8 copies.  Built once.
+int32_t ensure_sq8t(osk_view* v, hipStream_t st);
+// The wide kernel's inputs for a view (first batch the cost model sends to it).
+int32_t ensure_sq8w(osk_view* v, hipStream_t st);
+// The view's prefilter tables: int8 and 6-bit copies of its segments, settle slices, rounding bounds.  Built once.
+int32_t ensure_sq8(osk_view* v, hipStream_t st);
+// Settle slices over the wave lists of a tile table (list = tile·4 + wave), never spanning shards.
+void settle_slices(const std::vector<int32_t>& shard_tile_begin, std::vector<int4>& sl, std::vector<int32_t>& ssb);
+// Gather tiles for filtered scans over the compacted accepted ordinals (osk_filter.hip).  Built once.
+int32_t ensure_gather(osk_view* v, hipStream_t st);
+// the device's CUs (cached; the persistent kernels' grids and the wide tile table are sized by them)
+int view_cus(osk_view* v);
+
+// ---- the 6-bit tier's records (osk_api.hip), as the destructors need them
+// A segment being destroyed leaves the in-flight records of the 6-bit launches (which have completed).
+void sq6_forget_segment(const osk_seg* sg);
+// A view being destroyed leaves its share group (waits for the group's scans).
+void sq6_share_detach(osk_view* v);
+
 // Order this call's use of the view's workspace after the previous call's (another stream).
 int32_t order_after_last(osk_view* v, hipStream_t st);
 // A leased workspace slot of a view (host entries): `v` is the view or one of its replicas, `st` the

@@ -153,6 +153,49 @@ def test_warm_builds_copies_ahead_and_results_do_not_change():
         r.close()
 
 
+def test_footprint_is_every_allocation():
+    """osk_seg_footprint after staging, after registering parents and after each warm step is the sum of the
+    allocations the segment holds then, to the byte.  1,001 rows are no multiple of 16 or 128; 96 dims have no
+    6-bit tier, 24 float units and 6 int8 units."""
+    import ctypes as C
+    K_KS_ALIGN = 4                        # osk_internal.h kKsAlign
+    MFMA_KS = (2, 4, 6, 8, 12, 16)        # osk_sq8.hip kMfmaKS (sq8_mfma_ks: the first with 4·KS ≥ units8)
+    SLAB = 1024                           # bytes of one tiled slab: 16 rows × 64 int8 dims, or 8 rows × 32 dims × bf16 hi/lo
+    n, dim = 1001, 96
+    units, units8 = (dim + 3) // 4, (dim + 15) // 16
+    rows = O.synth(0, n, dim, 240, 3)
+    o2d = np.arange(n, dtype=np.int32) * 3 + 1
+    max_doc = 3 * n + 2
+    r = LU.GpuFlatVectorsReader("v", rows, COS, ord_to_doc=o2d, max_doc=max_doc)
+
+    def footprint():
+        b = C.c_int64()
+        _lib.check(_lib.lib().osk_seg_footprint(r.handle, C.byref(b)))
+        return b.value
+
+    try:
+        # padded rows, |x|² (cosine), ord→doc, the int8 copy and its 16-byte bound terms
+        want = n * units * 16 + n * 4 + n * 4 + n * units8 * 16 + n * 16
+        assert footprint() == want
+        parents = np.zeros(max_doc, bool)
+        parents[2::3] = True              # every vector's doc is followed by a parent doc
+        r.set_parents(parents)
+        want += n * 4                     # the row→parent table
+        assert footprint() == want
+        _lib.check(_lib.lib().osk_seg_warm(r.handle, _lib.OSK_WARM_PREFILTER_MFMA))
+        ks8 = next(ks for ks in MFMA_KS if 4 * ks >= units8)
+        want += -(-n // 16) * ks8 * SLAB  # the tiled int8 copy
+        assert footprint() == want
+        _lib.check(_lib.lib().osk_seg_warm(r.handle, _lib.OSK_WARM_BATCHED))
+        ks = -(-((units + 7) // 8) // K_KS_ALIGN) * K_KS_ALIGN   # 32-dim steps, rounded up to kKsAlign
+        want += max(1, -(-n // 128)) * 8 * ks * 2 * SLAB + n * 4 + 4   # bf16 hi/lo split, |x| rows, max |x|²
+        assert footprint() == want
+        _lib.check(_lib.lib().osk_seg_warm(r.handle, _lib.OSK_WARM_ALL))
+        assert footprint() == want
+    finally:
+        r.close()
+
+
 def test_host_entries_lease_concurrent_workspaces():
     """Concurrent synchronous host calls on ONE view / ONE segment each lease a workspace slot (the
     view or a replica over the same segments) with its own stream (osk_objects.h ViewLease): they run

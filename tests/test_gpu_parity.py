@@ -8,6 +8,8 @@ Bars:
     scores differ by ≤ TIE_ULPS ulps (a near-tie can legitimately reorder under another order).
 Scoring parity vs Lucene itself is unpinned (no Lucene jar in the reference) — see DESIGN.md.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -145,6 +147,10 @@ def test_empty_segment():
     try:
         s, d, c, v = r.search_batch(np.ones((2, 8), np.float32), 5)
         assert list(c) == [0, 0] and list(v) == [0, 0]
+        # every buffer of an empty segment holds one padded element: a row of 2 units, an int8 unit, 16 B of terms
+        b = C.c_int64()
+        _lib.check(_lib.lib().osk_seg_footprint(r.handle, C.byref(b)))
+        assert b.value == 2 * 16 + 16 + 16
     finally:
         r.close()
 
