@@ -295,11 +295,17 @@ int32_t osk_view_scan_time(osk_view* view, double* total_ms, int64_t* calls);
  *                     (default 1; needs "sq8" = 1 and no row outside the certificate's range): rows whose certified
  *                     score interval clears min_score on either side are decided there, the others are re-scored
  *                     exactly from the float32 rows.  0 = the float32 scan.  Same results.
+ *   "nest_sq8"        0|1 nested k-NN searches of float32 views read the int8 prefilter copy first (default 1;
+ *                     needs "sq8" = 1 and no row outside the certificate's range): the certified score intervals
+ *                     give each family a lower bound and each shard a floor, and only the rows that can still be
+ *                     the best child of a top-k family are re-scored exactly from the float32 rows (DESIGN.md
+ *                     §3i).  0 = the float32 scan.  Same results.
  * The testing build (libosknn_testing.so) also accepts "sq8_mfma_ablate", "mfma_ablate" (A/B timing,
  * results wrong), "sq8_force_fallback" (every prefilter list re-scanned exactly), "settle_trace" and
  * "thr_sq8_all_maybe" (the int8 first pass of a threshold search decides nothing: every accepted candidate
- * row is re-scored exactly; results unchanged) and "sq6_share_limit" (a shared 6-bit pass serves other views
- * only in its first N workgroups); the shipped library returns OSK_ERR_UNSUPPORTED for them. */
+ * row is re-scored exactly; results unchanged), "nest_sq8_all_settle" (the int8 first pass of a nested search
+ * rules nothing out: every row with a record is re-scored exactly; results unchanged) and "sq6_share_limit" (a
+ * shared 6-bit pass serves other views only in its first N workgroups); the shipped library returns OSK_ERR_UNSUPPORTED for them. */
 int32_t osk_tune_set(const char* key, int64_t value);
 
 /* Batched-path counters of a view: searches that took the MFMA path, and queries among them whose
@@ -316,7 +322,9 @@ int32_t osk_view_stats(osk_view* view, int64_t* batched_calls, int64_t* fallback
  * (such tiles), "sq8_rescored_rows" (rows re-scored exactly, all calls), "select_calls" (searches
  * on the select path, k > 12), "threshold_calls" (similarity-threshold searches), "threshold_sq8_calls" (those
  * that took the int8 first pass, knob "thr_sq8"), "threshold_sq8_settled_rows" (rows it left undecided and the
- * settle re-scored exactly, all calls), "nested_calls" (nested k-NN searches), "host_slots" (workspace slots the host entries have leased: 1 + replicas),
+ * settle re-scored exactly, all calls), "nested_calls" (nested k-NN searches), "nested_sq8_calls" (those that
+ * took the int8 first pass, knob "nest_sq8"), "nested_sq8_settled_rows" (rows its settle re-scored exactly, all
+ * calls), "host_slots" (workspace slots the host entries have leased: 1 + replicas),
  * "host_batches" / "host_batched_requests" (opportunistic batching of concurrent host calls).  The
  * search counters sum over the view and the replica slots its host entries leased.  osk_view_profile /
  * osk_view_scan_time time the device-entry calls on this view object only (per-call host timing:
@@ -406,10 +414,16 @@ int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, 
  *                families returned (≤ k), visited = accepted vectors scored (NaN rows included).  Joining a child
  *                to its parent stays with the caller ([L] ToParentBlockJoinQuery).
  *   scores       bit-identical to osk_seg_search's for the same row (device summation order).
- * Exact: one brute-force pass of the fp32 / int8 streaming scan.  Two limits:
+ * Exact: one brute-force pass over the corpus.  Byte fields take the int8 streaming scan.  A
+ * float32 view whose int8 prefilter copy certifies reads that copy (a quarter of the bytes) and re-scores from
+ * the float32 rows only the rows that can still be the best child of a top-k family (knob "nest_sq8"); a view
+ * holding a row outside the certificate's range, or "sq8" / "nest_sq8" = 0, takes the fp32 streaming scan.
+ * Limits:
  *   1 ≤ k ≤ 64 (the streaming scan's lists); a larger k returns OSK_ERR_UNSUPPORTED — routing large k through
  *   the select path is the follow-up;
- *   the certified int8 / 6-bit prefilters are not used, so a float32 search runs at the fp32 scan's rate.
+ *   the 6-bit tier is not used;
+ *   a query outside the certificate's range (a component beyond 2^±32) has no certificate: every accepted row is
+ *   re-scored, so such a call costs the int8 pass and then an fp32 pass (exact, and slower than "nest_sq8" = 0).
  * A null pointer, n_queries < 1 or k < 1 is OSK_ERR_INVALID (k > 64: OSK_ERR_UNSUPPORTED) before the device is
  * touched; without a device the entries return OSK_ERR_NO_DEVICE.  Multi-GPU nested search
  * (osk_shards_search_merge*) is not provided. */

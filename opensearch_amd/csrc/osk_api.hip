@@ -192,6 +192,8 @@ int32_t osk_tune_set(const char* key, int64_t value) {
         {"call_timing", &g_tuning.call_timing, 0, 1, false},
         {"thr_sq8", &g_tuning.thr_sq8, 0, 1, false},
         {"thr_sq8_all_maybe", &g_tuning.thr_sq8_all_maybe, 0, 1, true},
+        {"nest_sq8", &g_tuning.nest_sq8, 0, 1, false},
+        {"nest_sq8_all_settle", &g_tuning.nest_sq8_all_settle, 0, 1, true},
         {"sq8_mfma_ablate", &g_tuning.sq8_mfma_ablate, 0, 1023, true},   // (also sq6_scan's: 1 no re-bound, 2 no floor,
                                                                           // 16 loads only; sq6_rebound's: 256 no list work)
         {"sq8_force_fallback", &g_tuning.sq8_force_fallback, 0, 1, true},
@@ -2052,7 +2054,9 @@ int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const 
 
 // Core of osk_view_search_nested_device (caller holds the view mutex; device already set): passes of up to
 // kMaxNQ queries, each a clear of the pass's best-child keys, one corpus read (nest_scan) and the parent
-// tiles' top k (nest_topk); then merge_shards over the parent tiles, as over scan tiles.
+// tiles' top k (nest_topk); then merge_shards over the parent tiles, as over scan tiles.  On the int8 route a
+// pass is up to kNestSq8NQ queries and its corpus read is nest_scan_sq8, followed by the floor (nest_topk +
+// merge_shards over the lower-bound keys) and the exact settle into the same best-child keys.
 int32_t view_nested_device(osk_view* v, const void* d_queries, int nq, int k, const uint64_t* const* d_accept,
                            uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st) {
     OSK_REQUIRE(nq >= 1, "n_queries must be >= 1");
@@ -2070,16 +2074,60 @@ int32_t view_nested_device(osk_view* v, const void* d_queries, int nq, int k, co
         return zero_shard_hits(v, nq, k, d_shard_keys, d_shard_counts, d_visited, st);
     }
     const int UP = cfg_padded_units(v->cfg);
-    const int nq_pad = (nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;
+    const int nq_pad = (nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;   // (a multiple of kNestSq8NQ too)
     const size_t P = (size_t)v->nest_parents;
+    // float32 views whose int8 copy certifies take the int8 first pass (view_threshold_device's rule): the
+    // corpus is read once from the int8 copy, the rows that can still be the best child of a top-k family are
+    // re-scored exactly.  Every other view, and every byte field, keeps the fp32 / byte scan.
+    bool use8 = v->enc == ENC_FLOAT32 && v->n_tiles > 0 && g_tuning.nest_sq8.load(std::memory_order_relaxed) &&
+                g_tuning.sq8 && !(v->sq8_ready && !v->sq8_range_ok);
+    if (use8) {
+        if ((rc = ensure_sq8(v, st)) != OSK_OK) return rc;
+        use8 = v->sq8_range_ok;
+    }
+    const int pass = use8 ? kNestSq8NQ : kMaxNQ;
+    int64_t n_rows = 0;
+    for (const osk_seg* sg : v->segs) n_rows += sg->n_rows;
     OSK_HIP(v->ws_q.reserve((size_t)nq_pad * UP * 16));
     OSK_HIP(v->ws_nest_best.reserve(sizeof(uint64_t) * (size_t)std::min(nq, kMaxNQ) * P));
     OSK_HIP(v->ws_nest_cand.reserve(sizeof(uint64_t) * (size_t)nq * v->n_ptiles * k));
-    OSK_HIP(launch_prep_queries(d_queries, v->dim * elem_bytes(v->enc), nq, v->ws_q.p, UP, nq_pad, st));
+    if (use8) {   // the select path's fused prep: padded fp32 queries, |q|², int8 codes, bound terms, flags
+        const int u8 = v->units8;
+        OSK_HIP(v->ws_nest_ub.reserve(sizeof(uint32_t) * kNestSq8NQ * (size_t)n_rows));
+        OSK_HIP(v->ws_nest_lbkey.reserve(sizeof(uint64_t) * kNestSq8NQ * P));
+        OSK_HIP(v->ws_nest_fcand.reserve(sizeof(uint64_t) * kNestSq8NQ * (size_t)v->n_ptiles * k));
+        OSK_HIP(v->ws_nest_fkeys.reserve(sizeof(uint64_t) * kNestSq8NQ * (size_t)v->n_shards * k));
+        OSK_HIP(v->ws_nest_fcounts.reserve(sizeof(int32_t) * kNestSq8NQ * (size_t)v->n_shards));
+        OSK_HIP(v->ws_qnorm.reserve(sizeof(float) * nq_pad));
+        OSK_HIP(v->ws_q8.reserve((size_t)nq_pad * u8 * 16));
+        OSK_HIP(v->ws_qc.reserve(sizeof(float4) * nq_pad));
+        OSK_HIP(v->ws_flags.reserve(sizeof(int) * nq_pad));
+        OSK_HIP(launch_sq8_prep(v->cfg, static_cast<const float*>(d_queries), v->dim, nq, nq_pad, UP, u8,
+                                v->ws_q.as<float4>(), v->ws_qnorm.as<float>(), v->ws_q8.p, v->ws_qc.as<float4>(),
+                                v->ws_flags.as<int>(), st));
+    } else {
+        OSK_HIP(launch_prep_queries(d_queries, v->dim * elem_bytes(v->enc), nq, v->ws_q.p, UP, nq_pad, st));
+    }
     if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
     if ((rc = profile_sample(v, st, false)) != OSK_OK) return rc;
 
     NestParams p{};
+    if (use8) {
+        p.ub = v->ws_nest_ub.as<uint32_t>();
+        p.lbkey = v->ws_nest_lbkey.as<unsigned long long>();
+        p.floor_keys = v->ws_nest_fkeys.as<uint64_t>();
+        p.floor_counts = v->ws_nest_fcounts.as<int32_t>();
+        p.seg_vrow = v->d_seg_vrow.as<int64_t>();
+        p.rows8 = v->d_sq8_rows.as<const int4*>();
+        p.aux = v->d_sq8_aux.as<const float4*>();
+        p.settled = v->d_counters.as<unsigned long long>() + kCtrNestSettledRows;
+        p.n_rows = n_rows;
+        p.gam = v->sq8_gam;
+        p.g2 = v->sq8_g2;
+        p.units8 = v->units8;
+        p.n_shards = v->n_shards;
+        p.all_settle = g_tuning.nest_sq8_all_settle.load(std::memory_order_relaxed);
+    }
     p.segs = v->d_segs.as<SegDev>();
     p.tiles = v->d_tiles.as<TileDev>();
     p.nsegs = v->d_nest_segs.as<NestSeg>();
@@ -2095,18 +2143,41 @@ int32_t view_nested_device(osk_view* v, const void* d_queries, int nq, int k, co
     p.k = k;
     p.sim = v->sim;
     p.dim = v->dim;
-    for (int q0 = 0; q0 < nq; q0 += kMaxNQ) {
+    for (int q0 = 0; q0 < nq; q0 += pass) {
         p.q0 = q0;
-        p.q_count = std::min(kMaxNQ, nq - q0);
+        p.q_count = std::min(pass, nq - q0);
         p.q = v->ws_q.as<char>() + (size_t)q0 * UP * 16;
         OSK_HIP(hipMemsetAsync(p.best, 0, sizeof(uint64_t) * (size_t)p.q_count * P, st));
-        OSK_HIP(launch_nest_scan(v->enc, v->cfg, p, st, launch_ev_start(v, q0), launch_ev_stop(v, q0, nq)));
+        if (use8) {
+            OSK_HIP(hipMemsetAsync(p.lbkey, 0, sizeof(uint64_t) * (size_t)p.q_count * P, st));
+            // a filtered scan stores the records of the steps that hold an accepted row only: a row that is not
+            // accepted must have none
+            if (d_accept) OSK_HIP(hipMemsetAsync(p.ub, 0, sizeof(uint32_t) * (size_t)p.q_count * (size_t)n_rows, st));
+            p.q8 = v->ws_q8.as<int4>() + (size_t)q0 * v->units8;
+            p.qc = v->ws_qc.as<float4>() + q0;
+            p.qnorm = v->ws_qnorm.as<float>() + q0;
+            p.qflags = v->ws_flags.as<int>() + q0;
+            OSK_HIP(launch_nest_scan_sq8(v->cfg, p, st, launch_ev_start(v, q0), launch_ev_stop(v, q0, nq, pass)));
+            // the floor: the k best LBp keys of each shard, by the kernels that rank the best-child keys
+            NestParams f = p;
+            f.best = p.lbkey;
+            f.cand = v->ws_nest_fcand.as<uint64_t>();
+            f.q0 = 0;
+            OSK_HIP(launch_nest_topk(f, st));
+            OSK_HIP(launch_merge_shards(f.cand, v->n_ptiles, v->d_shard_ptile_begin.as<int32_t>(), v->n_shards,
+                                        p.q_count, k, v->ws_nest_fkeys.as<uint64_t>(),
+                                        v->ws_nest_fcounts.as<int32_t>(), st));
+            OSK_HIP(launch_nest_settle(v->cfg, p, st));
+        } else {
+            OSK_HIP(launch_nest_scan(v->enc, v->cfg, p, st, launch_ev_start(v, q0), launch_ev_stop(v, q0, nq)));
+        }
         OSK_HIP(launch_nest_topk(p, st));
     }
     if ((rc = profile_end(v, st, false)) != OSK_OK) return rc;
     OSK_HIP(launch_merge_shards(v->ws_nest_cand.as<uint64_t>(), v->n_ptiles, v->d_shard_ptile_begin.as<int32_t>(),
                                 v->n_shards, nq, k, d_shard_keys, d_shard_counts, st));
     v->nest_calls += 1;
+    v->nest_sq8_calls += use8 ? 1 : 0;
     return OSK_OK;
 }
 
@@ -2461,7 +2532,8 @@ int32_t osk_view_debug_copy(osk_view* v, const char* name, void* host, int64_t b
         {"akeys", &osk_view::ws_akeys},     {"cand_a", &osk_view::ws_cand_a},       {"flags", &osk_view::ws_flags},
         {"qsplit", &osk_view::ws_qsplit},   {"qnorm", &osk_view::ws_qnorm},         {"sq8cand", &osk_view::ws_sq8cand},
         {"sq8lb", &osk_view::ws_sq8lb},     {"qc", &osk_view::ws_qc},               {"settle_trace", &osk_view::ws_trace},
-        {"sel_lb", &osk_view::ws_sel_lb},   {"sel_ub", &osk_view::ws_sel_ub},
+        {"sel_lb", &osk_view::ws_sel_lb},   {"sel_ub", &osk_view::ws_sel_ub},       {"nest_ub", &osk_view::ws_nest_ub},
+        {"nest_lbkey", &osk_view::ws_nest_lbkey},
     };
     const DevBuf* b = nullptr;
     for (const auto& e : kBuffers)
@@ -2553,6 +2625,7 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
         {"threshold_calls", -1, &osk_view::thr_calls},
         {"threshold_sq8_calls", -1, &osk_view::thr_sq8_calls},
         {"nested_calls", -1, &osk_view::nest_calls},
+        {"nested_sq8_calls", -1, &osk_view::nest_sq8_calls},
         {"sq8_fallback_queries", kCtrFallbackQueries, nullptr},
         {"sq8_rescored_rows", kCtrRescoredRows, nullptr},
         {"sq8_exact_tiles", kCtrExactLists, nullptr},
@@ -2577,6 +2650,7 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
         {"sq8_rows_setup_barrier_cycles", kCtrRowsSetupBarrierCycles, nullptr},
         {"sq8_rows_setup_fragment_cycles", kCtrRowsSetupFragmentCycles, nullptr},
         {"threshold_sq8_settled_rows", kCtrThrSettledRows, nullptr},
+        {"nested_sq8_settled_rows", kCtrNestSettledRows, nullptr},
     };
     const auto* ctr = std::find_if(std::begin(kCounters), std::end(kCounters), [&](const auto& e) { return n == e.name; });
     OSK_REQUIRE(ctr != std::end(kCounters), "unknown counter: " + n);

@@ -150,7 +150,8 @@ enum Ctr : int {
     kCtrSq6TilesOwn = 23,          // sq6_scan_shared: tiles this view's launches scanned for its own query
     kCtrSq6TilesByOthers = 24,     // ...tiles of its queries that another view's launch had scanned
     kCtrSq6TilesHelped = 25,       // ...(query, tile) pairs its launches scanned for other views
-    kCtrCount = 26
+    kCtrNestSettledRows = 26,      // nest_settle_f32: rows re-scored
+    kCtrCount = 27
 };
 
 // What every prefilter scan kernel takes; each strategy's kernels take a struct derived from it, so a kernel
@@ -591,6 +592,9 @@ struct Tuning {
     std::atomic<int> thr_sq8{1};          // threshold search of float32 views: the certified int8 first pass
                                           // (thr_scan_sq8 + thr_settle_f32) instead of the fp32 scan (same results)
     std::atomic<int> thr_sq8_all_maybe{0};    // TESTING. thr_scan_sq8 classifies every accepted candidate row as maybe
+    std::atomic<int> nest_sq8{1};         // nested k-NN of float32 views: the certified int8 first pass
+                                          // (nest_scan_sq8 + nest_settle_f32) instead of the fp32 scan (same results)
+    std::atomic<int> nest_sq8_all_settle{0};  // TESTING. nest_settle_f32 re-scores every row that has a record
     std::atomic<int> sq8_force_fallback{0};   // TESTING. tests: every list of a prefiltered search is re-scanned exactly
     std::atomic<int> settle_trace{0};     // TESTING. A/B only: record settle phase timestamps (debug copy "settle_trace")
     std::atomic<int> mfma_ablate{0};      // TESTING. A/B only: 1 skip the epilogue, 2 skip query staging, 4 skip corpus staging,
@@ -663,7 +667,9 @@ hipError_t launch_thr_emit(int enc, int cfg, const ThrParams& p, hipStream_t s);
 // [L] DiversifyingChildrenFloat/ByteKnnVectorQuery.exactSearch.  One corpus pass (nest_scan_*: scan_f32 /
 // scan_i8 with the wave top-k list replaced by a 64-bit atomic max of the hit key into best[query][parent
 // slot]), a top k per parent tile (nest_topk), then merge_shards over the parent tiles.  At most kMaxNQ
-// queries share a corpus pass; k ≤ kScanMaxK.
+// queries share a corpus pass; k ≤ kScanMaxK.  Float32 views whose int8 copy certifies read that copy instead
+// (nest_scan_sq8: per-row upper bounds and per-parent lower bounds, ≤ kNestSq8NQ queries per pass) and re-score
+// exactly only the rows that can still be the best child of a top-k family (nest_settle_f32) into best.
 constexpr int kNestPtile = 4096;     // parent slots per nest_topk workgroup
 struct NestSeg {                     // per segment of a view
     const int32_t* row_parent;       // [n_rows] rank of the row's parent among the segment's parents
@@ -691,7 +697,27 @@ struct NestParams {
     int k;
     int sim;
     int dim;
+    // the certified int8 first pass (nest_scan_sq8 → floor → nest_settle_f32; float32 views, null / 0 otherwise)
+    uint32_t* ub;                    // [kNestSq8NQ][n_rows] sortable upper-bound score per (query, view row), 0 = no
+                                     // record; a segment's rows at seg_vrow[seg] (cleared before a filtered scan)
+    unsigned long long* lbkey;       // [q_count][n_parents] (sortable(LBp) << 32) | (0xFFFFFFFF − doc), 0 = none
+    const uint64_t* floor_keys;      // [q_count][n_shards][k] the k best lbkey of each shard, best first
+    const int32_t* floor_counts;     // [q_count][n_shards] how many of them exist (T = 0 below k)
+    const int64_t* seg_vrow;         // view row of each segment's ord 0
+    const int4* const* rows8;        // as ThrParams: the int8 copy, its bound terms, this pass's sq8_prep outputs
+    const float4* const* aux;
+    const int4* q8;
+    const float4* qc;
+    const float* qnorm;
+    const int* qflags;
+    unsigned long long* settled;     // [1] rows nest_settle_f32 re-scored (the view's device counter)
+    int64_t n_rows;                  // rows of the view (the stride of ub's queries)
+    float gam, g2;
+    int units8;
+    int n_shards;
+    int all_settle;                  // TESTING: every row with a record is settled
 };
+constexpr int kNestSq8NQ = 4;        // queries per int8 pass (thr_scan_sq8's)
 // Every launcher checks its grid, LDS and arguments and returns hipErrorInvalidValue instead of launching.
 // row_parent[row] = number of parent bits strictly below the row's doc (= the rank of nextSetBit(doc)):
 // word_rank[w] = parent bits in words [0, w), plus a popcount of the row's masked word.
@@ -700,6 +726,12 @@ hipError_t launch_nest_parents(const uint64_t* parent_bits, const int32_t* word_
 hipError_t launch_nest_scan(int enc, int cfg, const NestParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
                             hipEvent_t ev_stop = nullptr);
 hipError_t launch_nest_topk(const NestParams& p, hipStream_t s);
+// float32 views with the int8 copy: the corpus pass on it (ub records, lbkey), and — after nest_topk and
+// merge_shards over lbkey have given each shard's floor — the exact re-score of the rows that can still be a
+// best child of a top-k family into best (cfg: the view's float32 lane config)
+hipError_t launch_nest_scan_sq8(int cfg, const NestParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
+                                hipEvent_t ev_stop = nullptr);
+hipError_t launch_nest_settle(int cfg, const NestParams& p, hipStream_t s);
 hipError_t launch_row_norms_f32(const float4* rows, int64_t n_rows, int units, int cfg,
                                 float* out, hipStream_t s);
 hipError_t launch_row_norms_i8(const int4* rows, int64_t n_rows, int units, int32_t* out,

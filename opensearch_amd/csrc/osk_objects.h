@@ -283,7 +283,10 @@ struct osk_view {
     int64_t nest_parents = 0;
     int n_ptiles = 0;
     osk::DevBuf d_nest_segs, d_ptiles, d_shard_ptile_begin, ws_nest_best, ws_nest_cand;
-    int64_t nest_calls = 0;
+    // ...and of the int8 first pass (float32 views): the per-row upper-bound records and per-parent lower-bound
+    // keys of one pass (≤ kNestSq8NQ queries), the parent tiles' and the shards' floor lists
+    osk::DevBuf ws_nest_ub, ws_nest_lbkey, ws_nest_fcand, ws_nest_fkeys, ws_nest_fcounts;
+    int64_t nest_calls = 0, nest_sq8_calls = 0;   // nested searches; those that took the int8 first pass
     bool gather_ready = false;
     int n_gtiles = 0, n_gslices = 0;
     osk::DevBuf d_gtiles, d_gslices, d_gshard_slice_begin, d_seg_tiles;

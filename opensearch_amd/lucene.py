@@ -790,7 +790,8 @@ class DeviceShardSet:
     def counter(self, name: str) -> int:
         """A named counter of the view (osk_view_counter): "sq8_calls", "sq8_fallback_queries",
         "sq8_rescored_rows", "mfma_calls", "mfma_fallback_queries", "threshold_calls", "threshold_sq8_calls",
-        "threshold_sq8_settled_rows", "nested_calls"."""
+        "threshold_sq8_settled_rows", "nested_calls", "nested_sq8_calls" (nested searches that took the int8 first pass),
+        "nested_sq8_settled_rows" (rows their settle re-scored exactly)."""
         v = C.c_int64()
         check(lib().osk_view_counter(self.handle, name.encode(), C.byref(v)))
         return v.value

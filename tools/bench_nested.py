@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Nested k-NN against the fp32 streaming scan, same view, same run, interleaved.
+"""Nested k-NN — the fp32 scan and the certified int8 first pass — against the k-NN and threshold scans, same
+view, same run, interleaved.
 
   python tools/bench_nested.py [--rows-per-shard N] [--families 1,8,64] [--rounds R] [--iters I] [--out FILE]
 
@@ -11,8 +12,15 @@ rows — and, for one query at k = 10, measures round-robin:
   * nest_scan_f32  the nested scan's kernel time the same way: the same rows plus 4 B per row of the row→parent
                    table, plus one 64-bit atomic max per run of equal parents in a walk step;
   * the whole nested call on its stream (events around it): query prep + clear of the best-child keys + nest_scan +
-    nest_topk + merge_shards; call − scan bounds the clear + nest_topk + merge from above.
-Prints one JSON line.
+    nest_topk + merge_shards; call − scan bounds the clear + nest_topk + merge from above;
+  * nest_scan_sq8  the same call with tune nest_sq8 = 1 (the fp32 side runs with nest_sq8 = 0): the int8 pass's kernel
+                   time, the whole call (prep, clears, nest_scan_sq8, the floor's nest_topk + merge_shards,
+                   nest_settle_f32, nest_topk, merge_shards) and the rows the settle re-scored per call;
+  * thr_scan_sq8   the threshold search's int8 pass on the same view (min_score 0.99: next to nothing to settle or
+                   emit): the same loop without the parent fold, so nest_scan_sq8 / thr_scan_sq8 is what the fold
+                   costs.
+The knobs are switched per variant inside each round, so the variants alternate in one process.  Prints one JSON
+line.
 """
 import argparse
 import ctypes as C
@@ -42,11 +50,16 @@ def main():
     a = ap.parse_args()
     torch.cuda.set_device(0)
     dim, nsh, n, k = a.dim, 8, a.rows_per_shard, 10
-    _lib.tune("sq8", 0)   # fp32_stream: no prefilter copies, every k-NN search on the fp32 scan
     q_host = synth_host(0, 1, dim, 43, _lib.DIST_NORMALISH_UNIT)
     q = torch.from_numpy(q_host).cuda()
     keys = torch.empty((1, nsh, k), dtype=torch.int64, device="cuda")
     kcnt = torch.empty((1, nsh), dtype=torch.int32, device="cuda")
+    cap = 64
+    tmin = torch.full((1,), 0.99, dtype=torch.float32, device="cuda")
+    tdocs = torch.empty((1, nsh, cap), dtype=torch.int32, device="cuda")
+    tscores = torch.empty((1, nsh, cap), dtype=torch.float32, device="cuda")
+    tcount = torch.empty((1, nsh), dtype=torch.int32, device="cuda")
+    ttotal = torch.empty((1, nsh), dtype=torch.int64, device="cuda")
     torch.cuda.set_stream(torch.cuda.Stream())   # non-null: 0 would mean the library's own stream
     stream = torch.cuda.current_stream().cuda_stream
     corpus_gb = nsh * n * dim * 4 / 1e9
@@ -76,13 +89,27 @@ def main():
             _lib.check(L.osk_view_search_nested_device(view, q.data_ptr(), 1, k, None, keys.data_ptr(), kcnt.data_ptr(),
                                                        None, stream))
 
-        def timed(fn):
-            """(kernel ms per call from the scan launches' own stamps, stream ms per call around the calls)."""
+        def threshold():
+            _lib.check(L.osk_view_search_threshold_device(view, q.data_ptr(), 1, tmin.data_ptr(), None, cap, tdocs.data_ptr(),
+                                                          tscores.data_ptr(), tcount.data_ptr(), ttotal.data_ptr(), None,
+                                                          stream))
+
+        def counter(name):
+            v = C.c_int64()
+            _lib.check(L.osk_view_counter(view, name.encode(), C.byref(v)))
+            return v.value
+
+        def timed(fn, knobs):
+            """(kernel ms per call from the scan launches' own stamps, stream ms per call around the calls, rows the
+            nested settle re-scored per call)."""
+            for key, value in knobs.items():
+                _lib.tune(key, value)
             for _ in range(2):
                 fn()
             torch.cuda.synchronize()
             _lib.check(L.osk_view_profile(view, 1))
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s0 = counter("nested_sq8_settled_rows")
             e0.record()
             for _ in range(a.iters):
                 fn()
@@ -91,17 +118,28 @@ def main():
             ms, calls = C.c_double(), C.c_int64()
             _lib.check(L.osk_view_scan_time(view, C.byref(ms), C.byref(calls)))
             _lib.check(L.osk_view_profile(view, 0))
-            return ms.value / max(1, calls.value), e0.elapsed_time(e1) / a.iters
+            return (ms.value / max(1, calls.value), e0.elapsed_time(e1) / a.iters,
+                    (counter("nested_sq8_settled_rows") - s0) / a.iters)
 
-        variants = {"scan_f32": knn, "nest_scan_f32": nested}
+        # scan_f32: bench.py's `fp32_stream` configuration (no prefilter: every k-NN search on the fp32 scan)
+        variants = {"scan_f32": (knn, {"sq8": 0}), "nest_scan_f32": (nested, {"sq8": 1, "nest_sq8": 0}),
+                    "nest_scan_sq8": (nested, {"sq8": 1, "nest_sq8": 1}), "thr_scan_sq8": (threshold, {"sq8": 1, "thr_sq8": 1})}
         res = {name: [] for name in variants}
         for r in range(a.rounds):
-            for name, fn in variants.items():
-                res[name].append(timed(fn))
+            for name, (fn, knobs) in variants.items():
+                res[name].append(timed(fn, knobs))
             print(f"family {fam}: round {r} done", file=sys.stderr, flush=True)
+        c0 = counter("nested_sq8_calls")
         nested()
         torch.cuda.synchronize()
+        assert counter("nested_sq8_calls") - c0 == 1, "the int8 first pass did not run"
         families_returned = int(kcnt.sum().item())
+        keys8 = keys.clone()
+        _lib.tune("nest_sq8", 0)
+        nested()
+        torch.cuda.synchronize()
+        _lib.tune("nest_sq8", 1)
+        assert torch.equal(keys8, keys), "the two nested paths disagree"
 
         def med(name, i):
             return statistics.median(x[i] for x in res[name])
@@ -114,6 +152,16 @@ def main():
             "nest_scan_over_scan_f32": med("nest_scan_f32", 0) / med("scan_f32", 0),
             "nest_call_stream_ms": med("nest_scan_f32", 1),
             "nest_rest_ms_upper_bound": med("nest_scan_f32", 1) - med("nest_scan_f32", 0),
+            "nest_scan_sq8_kernel_ms": med("nest_scan_sq8", 0), "thr_scan_sq8_kernel_ms": med("thr_scan_sq8", 0),
+            "nest_scan_sq8_over_thr_scan_sq8": med("nest_scan_sq8", 0) / med("thr_scan_sq8", 0),
+            "nest_sq8_call_stream_ms": med("nest_scan_sq8", 1),
+            "nest_sq8_call_over_f32_call": med("nest_scan_sq8", 1) / med("nest_scan_f32", 1),
+            # prep + clears + the floor's nest_topk and merge_shards + nest_settle_f32 + nest_topk + merge_shards
+            "nest_sq8_rest_ms_upper_bound": med("nest_scan_sq8", 1) - med("nest_scan_sq8", 0),
+            # ...of which the fp32 call has all but the floor, the settle and one clear
+            "floor_and_settle_ms_upper_bound": (med("nest_scan_sq8", 1) - med("nest_scan_sq8", 0)) -
+                                               (med("nest_scan_f32", 1) - med("nest_scan_f32", 0)),
+            "settled_rows_per_call": med("nest_scan_sq8", 2),
             "per_round": {k_: [[round(x, 4) for x in p] for p in v] for k_, v in res.items()},
         }
         _lib.check(L.osk_view_release(view))
@@ -127,7 +175,6 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write(line + "\n")
-    _lib.tune("sq8", 1)
 
 
 if __name__ == "__main__":
