@@ -335,7 +335,13 @@ int32_t osk_view_counter(osk_view* view, const char* name, int64_t* value);
  * "qc", "settle_trace") to host memory.  "sel_lb" / "sel_ub": the select path's certified score bounds of
  * the last query searched with k > 12, one sortable u32 per view row (segment s's row r at the rows of the
  * segments before it + r; 0 = no record).  "sq8_lists": one int64, the wave lists per query of the last
- * prefiltered search ("sq8cand" / "sq8lb" are [queries][lists][16]). */
+ * prefiltered search ("sq8cand" / "sq8lb" are [queries][lists][16]).  Of the view's last 6-bit search (one
+ * query): "sq6cand" [lists][256] {u32 row, u32 float bits of the row's 6-bit test value} — list l is wave
+ * l & 3 of tile l >> 2 and holds the rows of that wave's share that passed the 6-bit test, row relative to
+ * the tile's segment; "sq6cnt" [lists] int32, the rows that passed (more than 256: the list overflowed and
+ * only the first 256 are stored); "sq6floor" u32, per shard 64 floor buckets then the floor cell, one every
+ * 16 words (sortable scores).  "sq6_tiles": the view's tile table, per tile {i32 seg, i32 shard, i64
+ * row_begin, i64 row_end} (a host copy). */
 int32_t osk_view_debug_copy(osk_view* view, const char* name, void* host, int64_t bytes);
 
 /* Device time of this thread's last synchronous host search (osk_seg_search / osk_view_search), for a

@@ -2525,6 +2525,11 @@ int32_t osk_view_debug_copy(osk_view* v, const char* name, void* host, int64_t b
         *static_cast<int64_t*>(host) = v->sq8_lists_last;
         return OSK_OK;
     }
+    if (n == "sq6_tiles") {   // (a host copy: the view's tile table, TileDev {i32 seg, i32 shard, i64 row_begin, i64 row_end})
+        OSK_REQUIRE((size_t)bytes <= sizeof(TileDev) * v->h_tiles.size(), "bytes exceed the tile table");
+        std::memcpy(host, v->h_tiles.data(), (size_t)bytes);
+        return OSK_OK;
+    }
     static const struct {
         const char* name;
         DevBuf osk_view::*buf;
@@ -2533,7 +2538,8 @@ int32_t osk_view_debug_copy(osk_view* v, const char* name, void* host, int64_t b
         {"qsplit", &osk_view::ws_qsplit},   {"qnorm", &osk_view::ws_qnorm},         {"sq8cand", &osk_view::ws_sq8cand},
         {"sq8lb", &osk_view::ws_sq8lb},     {"qc", &osk_view::ws_qc},               {"settle_trace", &osk_view::ws_trace},
         {"sel_lb", &osk_view::ws_sel_lb},   {"sel_ub", &osk_view::ws_sel_ub},       {"nest_ub", &osk_view::ws_nest_ub},
-        {"nest_lbkey", &osk_view::ws_nest_lbkey},
+        {"nest_lbkey", &osk_view::ws_nest_lbkey}, {"sq6cand", &osk_view::ws_cand6},   {"sq6cnt", &osk_view::ws_cnt6},
+        {"sq6floor", &osk_view::ws_floor},
     };
     const DevBuf* b = nullptr;
     for (const auto& e : kBuffers)

@@ -34,19 +34,22 @@ def g2(dim: int) -> float:
 
 
 class Quantised:
-    """The int8 form of float32 vectors [n, dim]: scale s (float32 value, held in float64), integer codes q
-    (float64), and the real norms A = s·|q|, B = |x − s·q|, x2 = |x|²."""
+    """The quantised form of float32 vectors [n, dim]: scale s = max|x|/levels (float32 value, held in
+    float64), integer codes q ∈ [-levels, levels] (float64), and the real norms A = s·|q|, B = |x − s·q|,
+    x2 = |x|².  levels 127: the int8 copy and query; the 6-bit tier (osk_sq6.hip) keeps its rows at 31 and
+    quantises its query at 119.  The Cauchy–Schwarz bound of `real_interval` holds for any quantiser, so
+    the intervals below are the 6-bit tier's as they stand."""
 
-    def __init__(self, x: np.ndarray):
+    def __init__(self, x: np.ndarray, levels: int = 127):
         x = np.ascontiguousarray(x, np.float32)
         assert x.ndim == 2
         with np.errstate(all="ignore"):
             m = np.abs(x).max(axis=1) if x.shape[1] else np.zeros(len(x), np.float32)
-            s = (m / np.float32(127.0)).astype(np.float32)            # one float32 division
+            s = (m / np.float32(levels)).astype(np.float32)           # one float32 division
             pos = s > 0
             ratio = np.zeros_like(x)
             np.divide(x, s[:, None], out=ratio, where=pos[:, None])   # float32 division
-            q = np.clip(np.rint(ratio), np.float32(-127.0), np.float32(127.0))
+            q = np.clip(np.rint(ratio), np.float32(-levels), np.float32(levels))
         q = np.where(pos[:, None], q, np.float32(0.0)).astype(np.float64)
         x64 = x.astype(np.float64)
         s64 = s.astype(np.float64)
@@ -142,6 +145,29 @@ def score_image(sim: int, lo, hi, qn=None, xn=None, dim=None):
             return np.where(zero, np.nan, a), np.where(zero, np.nan, b)
     a, b = score64(sim, lo, qn, xn), score64(sim, hi, qn, xn)
     return (b, a) if sim == EUCLIDEAN else (a, b)
+
+
+def floor_image(sim: int, lo, hi, qn=None, xn=None):
+    """The score every order's score of the row is at least, as the 6-bit tier's floor uses it (osk_sq6.hip
+    floor_lb_score): the score image of the interval's low side (its high side for EUCLIDEAN, whose transform
+    decreases), in float64 with the real norms."""
+    return score_image(sim, lo, hi, qn, xn)[0]
+
+
+SQ6_ROW_LEVELS, SQ6_QUERY_LEVELS = 31, 119
+
+
+def sq6_row_split(q):
+    """A row code q ∈ [-31, 31] as osk_sq6.hip's header states it: q = 4h + l, h = q >> 2 ∈ [-8, 7], l = q & 3."""
+    q = np.asarray(q, np.int64)
+    return q >> 2, q & 3
+
+
+def sq6_query_split(b):
+    """A query code b ∈ [-119, 119]: b = 16·bh + bl, bl = ((b + 8) & 15) − 8 ∈ [-8, 7], |bh| ≤ 7."""
+    b = np.asarray(b, np.int64)
+    bl = ((b + 8) & 15) - 8
+    return (b - bl) >> 4, bl
 
 
 def sortable(scores) -> np.ndarray:

@@ -220,15 +220,7 @@ def test_records_contain_the_real_interval(sim, dim, writer):
     assert not high.any(), f"LB above the real interval's image: {first(high)}"
 
 
-def declared_slack(sim, ref, dim):
-    """The raw-domain slack the source declares for the bound's own float arithmetic (osk_device.h
-    sq8_bounds): 2^-20·(|approx| + e) per side, e the whole radius; EUCLIDEAN 2^-20·(|x|² + |b|² + 2(|approx|
-    + e)) on d² before the (1 ± g2) factor."""
-    R, Q = ref["R"], ref["Q"]
-    base = R.x2[None, :] + Q.x2[:, None]
-    if int(sim) == BR.EUCLIDEAN:
-        return 2.0 ** -20 * (base + 2.0 * (np.abs(ref["c"]) + ref["r"])) * (1.0 + BR.g2(dim))
-    return 2.0 ** -20 * (np.abs(ref["c"]) + ref["r"] + BR.gam(dim) * base)
+declared_slack = BI.declared_slack   # (shared with test_gpu_sq6_bounds.py)
 
 
 TIGHTNESS = {}
