@@ -341,7 +341,11 @@ int32_t osk_view_counter(osk_view* view, const char* name, int64_t* value);
  * the tile's segment; "sq6cnt" [lists] int32, the rows that passed (more than 256: the list overflowed and
  * only the first 256 are stored); "sq6floor" u32, per shard 64 floor buckets then the floor cell, one every
  * 16 words (sortable scores).  "sq6_tiles": the view's tile table, per tile {i32 seg, i32 shard, i64
- * row_begin, i64 row_end} (a host copy). */
+ * row_begin, i64 row_end} (a host copy).  Of the view's last bf16×3 search: "akeys" [queries][shards][16] u64
+ * approximate (score, view row) keys, descending, and "acounts" [queries][shards] int32; "pkeys" /
+ * "pcounts", the same of the pilot (the first tile of each unit); "mfma_maxnorm2" [shards] float, the largest
+ * |x|² of each shard; "mfma_ks" one int64, the 32-dim K-steps of a padded row; "mfma_c" one double, the
+ * certificate's error constant. */
 int32_t osk_view_debug_copy(osk_view* view, const char* name, void* host, int64_t bytes);
 
 /* Device time of this thread's last synchronous host search (osk_seg_search / osk_view_search), for a

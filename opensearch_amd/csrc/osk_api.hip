@@ -2530,10 +2530,23 @@ int32_t osk_view_debug_copy(osk_view* v, const char* name, void* host, int64_t b
         std::memcpy(host, v->h_tiles.data(), (size_t)bytes);
         return OSK_OK;
     }
+    if (n == "mfma_ks" || n == "mfma_c") {   // (host values of the bf16×3 path, set by its first search on the view)
+        OSK_REQUIRE(v->mfma_ready, "the view has not taken the bf16x3 path yet");
+        if (n == "mfma_ks") {
+            OSK_REQUIRE(bytes == (int64_t)sizeof(int64_t), "mfma_ks is one int64");
+            *static_cast<int64_t*>(host) = v->mfma_KS;
+        } else {
+            OSK_REQUIRE(bytes == (int64_t)sizeof(double), "mfma_c is one double");
+            *static_cast<double*>(host) = v->mfma_c;
+        }
+        return OSK_OK;
+    }
     static const struct {
         const char* name;
         DevBuf osk_view::*buf;
     } kBuffers[] = {
+        {"acounts", &osk_view::ws_acounts}, {"pkeys", &osk_view::ws_pkeys},         {"pcounts", &osk_view::ws_pcounts},
+        {"mfma_maxnorm2", &osk_view::d_shard_maxnorm2},
         {"akeys", &osk_view::ws_akeys},     {"cand_a", &osk_view::ws_cand_a},       {"flags", &osk_view::ws_flags},
         {"qsplit", &osk_view::ws_qsplit},   {"qnorm", &osk_view::ws_qnorm},         {"sq8cand", &osk_view::ws_sq8cand},
         {"sq8lb", &osk_view::ws_sq8lb},     {"qc", &osk_view::ws_qc},               {"settle_trace", &osk_view::ws_trace},

@@ -599,8 +599,10 @@ struct Tuning {
     std::atomic<int> settle_trace{0};     // TESTING. A/B only: record settle phase timestamps (debug copy "settle_trace")
     std::atomic<int> mfma_ablate{0};      // TESTING. A/B only: 1 skip the epilogue, 2 skip query staging, 4 skip corpus staging,
                               // 8 force the full staging epilogue, 16 skip the pilot pass, 32 skip the
-                              // main epilogue's quick tests, 64 skip its merge (barriers + list inserts)
-                              // (results are wrong and the exact fallback is skipped)
+                              // main epilogue's quick tests (every pair takes the exact test), 64 skip its
+                              // merge (barriers + list inserts)
+                              // (1, 2, 4, 64 and 128 give wrong results; 8, 16 and 32 leave the candidates
+                              // as they are, tests/test_gpu_mfma_cert.py; the exact fallback is skipped under all)
 };
 extern Tuning g_tuning;
 

@@ -13,7 +13,10 @@
 // where the bound covers the split, the fp32 accumulation and the device-order rounding
 // (|Σ approx − Σ device| ≤ c·|x|·|q|, c from Kpad).  A query whose certificate fails for any shard
 // is recomputed by the exact streaming scan.  Results are therefore bit-identical to the
-// streaming path (and to the ORDER_DEVICE oracle) — asserted by tests/test_gpu_parity.py.
+// streaming path (and to the ORDER_DEVICE oracle).  tests/test_gpu_batched.py asserts that on final
+// lists; tests/test_gpu_mfma_cert.py reads the split, the candidates and the flags back and holds
+// them, the error model e ≤ U(a) included, to oracle/mfma_reference.py ("Parity of the
+// bf16×3 path").
 #include "osk_internal.h"
 #include "osk_wave.h"
 
@@ -84,10 +87,11 @@ __global__ __launch_bounds__(kBlock) void max_norm2(const float* __restrict__ xn
     if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
 }
 
-// |x| per row (the cosine bound of the candidate epilogue)
+// |x| per row (the cosine bound of the candidate epilogue, its only reader).  NaN where |x|² is below 2^-64:
+// the quick test d ≥ cq·|x| lets a NaN pass, so such a row always reaches approx_score, which scores it +inf.
 __global__ __launch_bounds__(kBlock) void row_sqrt(const float* __restrict__ xn, int64_t n, float* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-        out[i] = sqrtf(xn[i]);
+        out[i] = xn[i] >= 0x1p-64f ? sqrtf(xn[i]) : __builtin_nanf("");
 }
 
 hipError_t launch_row_sqrt(const float* xn, int64_t n, float* out, hipStream_t s) {
@@ -148,15 +152,30 @@ __device__ __forceinline__ void glds4(const void* g, char* lds_base) {
                                      (__attribute__((address_space(3))) void*)lds_base, 4, 0, 0);
 }
 
+// A NaN approximate score (inf − inf among the accumulated products) says nothing about the exact one, which
+// sums in another order: make_key would drop the row unseen.  +inf keeps it a candidate, re-scored exactly,
+// and at the k'-th place it fails the certificate.
+__device__ __forceinline__ float cand_score(float s) { return s != s ? __builtin_inff() : s; }
+
 __device__ __forceinline__ float approx_score(int sim, float d, float qn, float xn) {
     switch (sim) {
         case SIM_EUCLIDEAN: {
             const float d2 = fmaxf(xn + qn - 2.0f * d, 0.0f);
             return 1.0f / (1.0f + d2);
         }
-        case SIM_DOT_PRODUCT: return (1.0f + d) * 0.5f;
-        case SIM_COSINE: return (1.0f + d * rsqrtf(qn * xn)) * 0.5f;
-        default: return d < 0.0f ? 1.0f / (1.0f - d) : d + 1.0f;
+        // (max(0, ·) as the exact transform: below it a row scoring 0 ties the k-th hit from outside the candidates)
+        case SIM_DOT_PRODUCT: return fmaxf(cand_score((1.0f + d) * 0.5f), 0.0f);
+        case SIM_COSINE: {
+            // Each norm has its own rsqrt: the product |q|²·|x|² leaves float's range from components near
+            // 2^±32 at a few hundred dims (+inf → rsqrt 0 → every row of the shard scored exactly 0.5 and the
+            // certificate passed on the 16 lowest rows; → 0 or subnormal at the other end).  Below 2^-64, the
+            // least |v|² of a vector the certified range holds (zero vectors included), a norm has no error
+            // model: +inf.  Such a row always gets here: row_sqrt stages its |x| as NaN, which passes the quick
+            // test; under such a query the pilot's threshold is +inf, its loosened form NaN, and every pair passes.
+            const float s = (1.0f + d * rsqrtf(qn) * rsqrtf(xn)) * 0.5f;
+            return qn >= 0x1p-64f && xn >= 0x1p-64f ? cand_score(s) : __builtin_inff();
+        }
+        default: return cand_score(d < 0.0f ? 1.0f / (1.0f - d) : d + 1.0f);
     }
 }
 
@@ -361,7 +380,7 @@ __global__ __launch_bounds__(kMB) void mfma_cand(MfmaParams p) {
             // 2^-16·max(1, |t|) (far above the rounding of either form), evaluated branch-free as
             //   α·d − β·v_row ≥ γ_q:
             //   COSINE      α = 1, β = cq_q, v = |x|, γ = 0              (d ≥ cq·|x|)
-            //   DOT / MIP   α = 1, β = 0, γ = cq_q                       (d ≥ cq)
+            //   DOT / MIP   α = 1, β = 0, γ = cq_q                       (d ≥ cq; every pair when tm ≤ 0)
             //   EUCLIDEAN   α = 2, β = 1 − 2^-18, v = |x|², γ = |q|² − D − 2^-18·(|q|² + D), D = 1/tm − 1
             //               (1/(1 + max(|x|² + |q|² − 2d, 0)) ≥ tm ⟸ 2d − |x|² ≥ |q|² − D; the 2^-18 terms
             //               cover the float rounding of both sides, 2|d| ≤ |x|² + |q|²)
@@ -383,7 +402,7 @@ __global__ __launch_bounds__(kMB) void mfma_cand(MfmaParams p) {
                 float c = -__builtin_inff();
                 if (thr_l[j] != 0u) {
                     if (sim == SIM_COSINE) c = (2.0f * tm - 1.0f) * sqrtf(qn_l[j]);
-                    else if (sim == SIM_DOT_PRODUCT) c = 2.0f * tm - 1.0f;
+                    else if (sim == SIM_DOT_PRODUCT && tm > 0.0f) c = 2.0f * tm - 1.0f;   // (t ≈ 0: the clamped scores tie it)
                     else if (sim == SIM_MIP && tm > 0.0f) c = tm >= 1.0f ? tm - 1.0f : 1.0f - 1.0f / tm;
                     else if (l2 && tm > 0.0f) {
                         const float D = 1.0f / tm - 1.0f, qn = qn_l[j];
@@ -408,7 +427,12 @@ __global__ __launch_bounds__(kMB) void mfma_cand(MfmaParams p) {
             uint32_t mh[2] = {0u, 0u};   // pass masks per half tile: bit (i & 3)·8 + r·2 + j
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                if (p.ablate & 32) break;   // A/B: no quick tests
+                if (p.ablate & 32) {   // A/B: no quick tests, every pair of a real query takes the exact test
+                    // (same candidates; a padded column would fill its slots and send every tile down the full path)
+                    const int q0 = qblock * 256 + wave * 32 + (lane & 15);
+                    mh[0] = mh[1] = (q0 < p.nq ? 0x55555555u : 0u) | (q0 + 16 < p.nq ? 0xAAAAAAAAu : 0u);
+                    break;
+                }
                 const int rl0 = i * 16 + (lane >> 4) * 4;
                 const float4 v4 = (cosine || l2) ? *reinterpret_cast<const float4*>(vrow + rl0)
                                                  : make_float4(0.f, 0.f, 0.f, 0.f);
