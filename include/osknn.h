@@ -95,6 +95,29 @@ extern "C" {
 #define OSK_COSINE                2
 #define OSK_MAXIMUM_INNER_PRODUCT 3
 
+/* ---- binary vectors: exact Hamming k-NN over packed bits ----
+ * OSK_HAMMING is not a Lucene ordinal: it is this library's similarity for OpenSearch k-NN's
+ * {"data_type": "binary", "space_type": "hamming"} fields.  It is accepted with encoding OSK_BYTE only
+ * (with OSK_FLOAT32: OSK_ERR_INVALID).
+ *   field     `dim` is the number of BYTES per vector, in [1, OSK_MAX_DIM]; the field has 8·dim bits.  Rows and
+ *             queries are arrays of dim bytes (int8 or uint8: the same bits); bit order inside a byte is
+ *             irrelevant.
+ *   distance  d(q, x) = popcount(q XOR x) over the dim bytes, an exact integer in [0, 8·dim].
+ *   score     1.0f / (1.0f + (float)d) — OpenSearch k-NN's translation of the Hamming space, the float
+ *             operations of the byte EUCLIDEAN score; in (0, 1], never NaN, bit-exact (no tolerance anywhere).
+ *   order     score descending, then doc ascending (the hit keys of every other field).  Hamming scores tie
+ *             massively — 8 bits give nine distinct scores — so the tie rule decides most cuts.
+ * Everything else is as osk_seg_search documents: accept bitsets, sparse ord_to_doc, visited = the accepted
+ * vectors scored, unused slots −inf / INT32_MAX, 1 ≤ k ≤ OSK_MAX_K.  A Hamming segment keeps no per-row norms
+ * (its osk_seg_footprint is 4 B per row below a byte EUCLIDEAN segment's of the same rows); osk_seg_warm and
+ * osk_view_warm are no-ops for it, as for every byte field.
+ * Served: osk_seg_search, osk_view_search, osk_view_search_device, osk_shards_search_merge and
+ * osk_shards_search_merge_device.  Not served: the similarity-threshold (radial) and the nested entries return
+ * OSK_ERR_UNSUPPORTED for a Hamming segment or view, before the device is touched (osk_seg_set_parents stays
+ * allowed: it does not look at the vectors).  Radial and nested Hamming search are the follow-up.
+ * Tuning knob "ham_stream" (0|1, default 1): one unfiltered query scans on scan_ham_stream; 0 = scan_ham. */
+#define OSK_HAMMING 4
+
 /* ---- synthetic corpus distributions (bench / tests) ---- */
 #define OSK_DIST_UNIFORM01      0   /* U[0,1)                         (C1)            */
 #define OSK_DIST_UNIFORM01_X128 1   /* U[0,1)·128, SIFT-like          (C2)            */

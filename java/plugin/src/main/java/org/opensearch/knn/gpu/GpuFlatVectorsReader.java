@@ -78,13 +78,19 @@ public final class GpuFlatVectorsReader extends KnnVectorsReader {
             }
             MemorySegment out = arena.allocate(ADDRESS);
             OsKnn.check((int) OsKnn.SEG_STAGE.invokeExact(device, rows, (long) n, dim,
-                bytes ? OsKnn.OSK_BYTE : OsKnn.OSK_FLOAT32, field.getVectorSimilarityFunction().ordinal(), ordToDoc,
+                bytes ? OsKnn.OSK_BYTE : OsKnn.OSK_FLOAT32, similarityOf(field, bytes), ordToDoc,
                 maxDoc, out));
             segs.put(field.name, out.get(ADDRESS, 0));
             encodings.put(field.name, field.getVectorEncoding());
         } catch (Throwable t) {
             throw OsKnn.wrap(t);
         }
+    }
+
+    /** libosknn's similarity of a field: the Lucene ordinal, or OSK_HAMMING for a byte field the mapper marked binary. */
+    static int similarityOf(FieldInfo field, boolean bytes) {
+        boolean binary = bytes && "true".equals(field.getAttribute(KnnVectorFieldMapper.BINARY_ATTRIBUTE));
+        return binary ? OsKnn.OSK_HAMMING : field.getVectorSimilarityFunction().ordinal();
     }
 
     /** The field's osk_seg* (GpuShardViews groups a shard's segments into one osk_view). */

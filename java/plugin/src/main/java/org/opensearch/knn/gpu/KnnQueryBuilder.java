@@ -123,9 +123,10 @@ public final class KnnQueryBuilder extends AbstractQueryBuilder<KnnQueryBuilder>
         MappedFieldType mft = context.fieldMapper(field);
         if (mft == null || !(mft.unwrap() instanceof KnnVectorFieldMapper.KnnVectorFieldType ft))
             throw new QueryShardException(context, "[knn] field [" + field + "] is not a knn_vector field");
-        if (vector.length != ft.dimension())
+        // (a binary field's dimension counts bits: its vectors hold dimension / 8 integers in [-128, 127])
+        if (vector.length != ft.vectorLength())
             throw new QueryShardException(context, "[knn] vector has " + vector.length + " dims, field [" + field + "] "
-                + ft.dimension());
+                + ft.vectorLength());
         Query f = filter == null ? null : filter.toQuery(context);
         return ft.isByte() ? new GpuKnnByteVectorQuery(field, ft.toBytes(vector), k, f)
                            : new GpuKnnFloatVectorQuery(field, vector, k, f);

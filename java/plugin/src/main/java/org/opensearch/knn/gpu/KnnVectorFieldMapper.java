@@ -2,9 +2,14 @@
  * The `knn_vector` field (MapperPlugin.getMappers, S/plugins/MapperPlugin.java:59):
  *   {"type": "knn_vector", "dimension": 768, "data_type": "float" | "byte",
  *    "space_type": "l2" | "innerproduct" | "cosinesimil" | "dot_product", "method": {...}}
+ *   {"type": "knn_vector", "dimension": 768, "data_type": "binary", "space_type": "hamming"}
  * indexed as Lucene's KnnFloatVectorField / KnnByteVectorField with the space type's VectorSimilarityFunction;
- * the codec (GpuKnnCodec) gives the field GpuFlatVectorsFormat.  Python mirror and contract tests:
- * opensearch_amd/dsl.py, tests/test_dsl.py.
+ * the codec (GpuKnnCodec) gives the field GpuFlatVectorsFormat.  A binary field holds packed bits: its dimension
+ * counts bits (a multiple of 8, at most 8 x MAX_DIMS), a vector is dimension / 8 integers in [-128, 127], and
+ * space_type is hamming (its default; no other pairs with binary, and hamming pairs with nothing else).  Lucene
+ * can only record one of its own similarity ordinals, so the field is written as a byte field under EUCLIDEAN
+ * with the field attribute BINARY_ATTRIBUTE, and GpuFlatVectorsReader stages it with OSK_HAMMING.  Python
+ * mirror and contract tests: opensearch_amd/dsl.py, tests/test_dsl.py, tests/test_hamming_cpu.py.
  */
 package org.opensearch.knn.gpu;
 
@@ -35,8 +40,12 @@ import org.opensearch.search.lookup.SearchLookup;
 public final class KnnVectorFieldMapper extends ParametrizedFieldMapper {
     public static final String CONTENT_TYPE = "knn_vector";
 
+    /** FieldInfo attribute of a binary (packed bits, Hamming) field: the reader stages it with OSK_HAMMING. */
+    public static final String BINARY_ATTRIBUTE = "knn_vector.binary";
+
     static VectorSimilarityFunction similarity(String spaceType) {
         switch (spaceType) {
+            case "hamming": return VectorSimilarityFunction.EUCLIDEAN;   // the ordinal Lucene records; see above
             case "l2": return VectorSimilarityFunction.EUCLIDEAN;
             case "innerproduct": return VectorSimilarityFunction.MAXIMUM_INNER_PRODUCT;
             case "cosinesimil": return VectorSimilarityFunction.COSINE;
@@ -52,13 +61,15 @@ public final class KnnVectorFieldMapper extends ParametrizedFieldMapper {
     public static final class Builder extends ParametrizedFieldMapper.Builder {
         private final Parameter<Integer> dimension = Parameter.intParam("dimension", false, m -> toType(m).dimension, -1)
             .setValidator(d -> {
-                if (d < 1 || d > GpuFlatVectorsFormat.MAX_DIMS)
-                    throw new IllegalArgumentException("dimension must be in [1, " + GpuFlatVectorsFormat.MAX_DIMS + "], got " + d);
+                // (binary: bits, up to 8 x MAX_DIMS; build() checks the range of the field's own data_type)
+                if (d < 1 || d > 8 * GpuFlatVectorsFormat.MAX_DIMS)
+                    throw new IllegalArgumentException("dimension must be in [1, " + GpuFlatVectorsFormat.MAX_DIMS
+                        + "] (binary: a multiple of 8 in [8, " + 8 * GpuFlatVectorsFormat.MAX_DIMS + "]), got " + d);
             });
         private final Parameter<String> dataType = Parameter.restrictedStringParam("data_type", false,
-            m -> toType(m).dataType, "float", "byte");
+            m -> toType(m).dataType, "float", "byte", "binary");
         private final Parameter<String> spaceType = Parameter.restrictedStringParam("space_type", false,
-            m -> toType(m).spaceType, "l2", "innerproduct", "cosinesimil", "dot_product");
+            m -> toType(m).spaceType, "l2", "innerproduct", "cosinesimil", "dot_product", "hamming");
         private final Parameter<Map<String, String>> meta = Parameter.metaParam();
 
         public Builder(String name) {
@@ -70,11 +81,28 @@ public final class KnnVectorFieldMapper extends ParametrizedFieldMapper {
             return List.of(dimension, dataType, spaceType, meta);
         }
 
+        /** space_type as written, or its default: hamming for a binary field, l2 otherwise. */
+        String resolvedSpaceType() {
+            boolean binary = "binary".equals(dataType.getValue());
+            return spaceType.isConfigured() ? spaceType.getValue() : (binary ? "hamming" : "l2");
+        }
+
         @Override
         public KnnVectorFieldMapper build(BuilderContext context) {
-            KnnVectorFieldType ft = new KnnVectorFieldType(buildFullName(context), dimension.getValue(),
-                "byte".equals(dataType.getValue()) ? VectorEncoding.BYTE : VectorEncoding.FLOAT32,
-                similarity(spaceType.getValue()), meta.getValue());
+            boolean binary = "binary".equals(dataType.getValue());
+            String space = resolvedSpaceType();
+            int d = dimension.getValue();
+            if (binary != "hamming".equals(space))
+                throw new IllegalArgumentException("[space_type] hamming and [data_type] binary go together only: got "
+                    + "[space_type] " + space + " with [data_type] " + dataType.getValue());
+            if (binary ? (d < 8 || d % 8 != 0) : d > GpuFlatVectorsFormat.MAX_DIMS)
+                throw new IllegalArgumentException(binary
+                    ? "dimension of a [data_type] binary field must be a multiple of 8 in [8, "
+                        + 8 * GpuFlatVectorsFormat.MAX_DIMS + "], got " + d
+                    : "dimension must be in [1, " + GpuFlatVectorsFormat.MAX_DIMS + "], got " + d);
+            KnnVectorFieldType ft = new KnnVectorFieldType(buildFullName(context), d,
+                "float".equals(dataType.getValue()) ? VectorEncoding.FLOAT32 : VectorEncoding.BYTE,
+                similarity(space), binary, meta.getValue());
             return new KnnVectorFieldMapper(name, ft, multiFieldsBuilder.build(this, context), copyTo.build(), this);
         }
     }
@@ -86,17 +114,29 @@ public final class KnnVectorFieldMapper extends ParametrizedFieldMapper {
         private final int dimension;
         private final VectorEncoding encoding;
         private final VectorSimilarityFunction similarity;
+        private final boolean binary;
 
         public KnnVectorFieldType(String name, int dimension, VectorEncoding encoding, VectorSimilarityFunction similarity,
-                                  Map<String, String> meta) {
+                                  boolean binary, Map<String, String> meta) {
             super(name, false, false, false, TextSearchInfo.NONE, meta);
             this.dimension = dimension;
             this.encoding = encoding;
             this.similarity = similarity;
+            this.binary = binary;
         }
 
         public int dimension() {
             return dimension;
+        }
+
+        /** Packed bits under Hamming distance (data_type binary): dimension counts bits. */
+        public boolean isBinary() {
+            return binary;
+        }
+
+        /** Elements of a document / query vector, the Lucene field's dimension: dimension, or (binary) dimension / 8. */
+        public int vectorLength() {
+            return binary ? dimension / 8 : dimension;
         }
 
         public boolean isByte() {
@@ -146,7 +186,7 @@ public final class KnnVectorFieldMapper extends ParametrizedFieldMapper {
         super(simpleName, ft, multiFields, copyTo);
         this.dimension = b.dimension.getValue();
         this.dataType = b.dataType.getValue();
-        this.spaceType = b.spaceType.getValue();
+        this.spaceType = b.resolvedSpaceType();
     }
 
     @Override
@@ -162,13 +202,19 @@ public final class KnnVectorFieldMapper extends ParametrizedFieldMapper {
             throw new IllegalArgumentException("knn_vector field [" + name() + "] expects an array of numbers");
         for (XContentParser.Token t = parser.nextToken(); t != XContentParser.Token.END_ARRAY; t = parser.nextToken())
             values.add(parser.floatValue());
-        if (values.size() != dimension)
-            throw new IllegalArgumentException("vector of field [" + name() + "] has " + values.size() + " dims, the mapping "
-                + dimension);
         KnnVectorFieldType ft = fieldType();
+        if (values.size() != ft.vectorLength())
+            throw new IllegalArgumentException("vector of field [" + name() + "] has " + values.size() + " dims, the mapping "
+                + ft.vectorLength());
         float[] v = new float[values.size()];
         for (int i = 0; i < v.length; i++) v[i] = values.get(i);
-        if (ft.isByte()) {
+        if (ft.isBinary()) {
+            FieldType binaryType = new FieldType();
+            binaryType.setVectorAttributes(v.length, VectorEncoding.BYTE, ft.similarity());
+            binaryType.putAttribute(BINARY_ATTRIBUTE, "true");
+            binaryType.freeze();
+            context.doc().add(new KnnByteVectorField(ft.name(), ft.toBytes(v), binaryType));
+        } else if (ft.isByte()) {
             context.doc().add(new KnnByteVectorField(ft.name(), ft.toBytes(v), ft.similarity()));
         } else {
             context.doc().add(new KnnFloatVectorField(ft.name(), v, ft.similarity()));

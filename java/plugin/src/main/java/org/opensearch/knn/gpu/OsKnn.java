@@ -23,6 +23,8 @@ final class OsKnn {
 
     static final int OSK_FLOAT32 = 0;
     static final int OSK_BYTE = 1;
+    /** osknn.h OSK_HAMMING: packed bits with OSK_BYTE; not a Lucene VectorSimilarityFunction ordinal. */
+    static final int OSK_HAMMING = 4;
     static final int OSK_WARM_PREFILTER_MFMA = 2;
     static final int OSK_COMM_ID_BYTES = 128;
 

@@ -40,6 +40,7 @@ EUCLIDEAN = 0
 DOT_PRODUCT = 1
 COSINE = 2
 MAXIMUM_INNER_PRODUCT = 3
+OSK_HAMMING = 4            # include/osknn.h OSK_HAMMING: packed bits, OSK_BYTE only (not a Lucene ordinal)
 
 DIST_UNIFORM01 = 0
 DIST_UNIFORM01_X128 = 1

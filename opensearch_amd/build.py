@@ -29,7 +29,7 @@ LIB_TESTING = PKG / "libosknn_testing.so"
 TESTING_VARIANTS = ("osk_api.hip", "osk_sq8.hip", "osk_sq8w.hip", "osk_sq6.hip", "osk_comm.hip")
 OBJDIR = ROOT / "build" / "osknn"
 
-SOURCES = ["osk_kernels.hip", "osk_mfma.hip", "osk_sq8.hip", "osk_sq8w.hip", "osk_sq6.hip", "osk_filter.hip", "osk_select.hip", "osk_threshold.hip", "osk_nested.hip", "osk_api.hip", "osk_derived.hip", "osk_comm.hip", "osk_host.cpp"]
+SOURCES = ["osk_kernels.hip", "osk_mfma.hip", "osk_sq8.hip", "osk_sq8w.hip", "osk_sq6.hip", "osk_filter.hip", "osk_select.hip", "osk_threshold.hip", "osk_nested.hip", "osk_hamming.hip", "osk_api.hip", "osk_derived.hip", "osk_comm.hip", "osk_host.cpp"]
 HEADERS = ["osk_common.h", "osk_internal.h", "osk_wave.h", "osk_objects.h", "osk_device.h", "osk_rowscore.h"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

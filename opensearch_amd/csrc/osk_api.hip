@@ -189,6 +189,7 @@ int32_t osk_tune_set(const char* key, int64_t value) {
         {"sq6_share_limit", &g_tuning.sq6_share_limit, -1, 1 << 24, true},
         {"sq8_mfma_ring", &g_tuning.sq8_mfma_ring, -1, 8, false},
         {"i8_stream", &g_tuning.i8_stream, 0, 1, false},
+        {"ham_stream", &g_tuning.ham_stream, 0, 1, false},
         {"call_timing", &g_tuning.call_timing, 0, 1, false},
         {"thr_sq8", &g_tuning.thr_sq8, 0, 1, false},
         {"thr_sq8_all_maybe", &g_tuning.thr_sq8_all_maybe, 0, 1, true},
@@ -757,7 +758,8 @@ int32_t stream_search(osk_view* v, const void* qpad, const void* qnorm, int nq, 
                       const uint64_t* const* d_accept, uint64_t* d_shard_keys, int32_t* d_shard_counts,
                       int64_t* d_visited, hipStream_t st) {
     OSK_HIP(v->ws_cand.reserve(sizeof(uint64_t) * (size_t)nq * v->n_tiles * k));
-    ScanParams p{};
+    HamParams p{};   // (a Hamming view's launches read q_units; every other launch takes the ScanParams base)
+    p.q_units = UP;
     p.segs = v->d_segs.as<SegDev>();
     p.tiles = v->d_tiles.as<TileDev>();
     p.accept = d_accept;
@@ -775,7 +777,10 @@ int32_t stream_search(osk_view* v, const void* qpad, const void* qnorm, int nq, 
         p.q = static_cast<const char*>(qpad) + (size_t)q0 * UP * 16;
         p.qnorm_f = static_cast<const float*>(qnorm) + q0;
         p.qnorm_i = static_cast<const int32_t*>(qnorm) + q0;
-        OSK_HIP(launch_scan(v->enc, v->cfg, qc, p, st, launch_ev_start(v, q0), launch_ev_stop(v, q0, nq)));
+        if (v->sim == SIM_HAMMING)   // packed bits: osk_hamming.hip's scans (no norms; their own lane configs)
+            OSK_HIP(launch_scan_ham(qc, p, st, launch_ev_start(v, q0), launch_ev_stop(v, q0, nq)));
+        else
+            OSK_HIP(launch_scan(v->enc, v->cfg, qc, p, st, launch_ev_start(v, q0), launch_ev_stop(v, q0, nq)));
     }
     int32_t rc = profile_end(v, st, false);
     if (rc) return rc;
@@ -2318,6 +2323,14 @@ int32_t osk_testing_sq6_resume(osk_view* view) {
 }
 #endif
 
+// Packed-bit fields (osknn.h OSK_HAMMING) are served by the k-NN entries only: every threshold and nested entry
+// refuses them here, before the device is touched (radial and nested Hamming search are not built).
+static int32_t refuse_hamming(int sim, const char* what) {
+    if (sim != SIM_HAMMING) return OSK_OK;
+    set_error(std::string(what) + " is not served for Hamming (OSK_HAMMING) fields");
+    return OSK_ERR_UNSUPPORTED;
+}
+
 int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, int32_t n_queries,
                                          const float* d_min_scores, const uint64_t* const* d_accept, int32_t cap,
                                          int32_t* d_docs, float* d_scores, int32_t* d_count, int64_t* d_total,
@@ -2328,7 +2341,9 @@ int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, 
     OSK_REQUIRE(d_queries && d_min_scores && d_docs && d_scores && d_count && d_total, "null device buffer");
     OSK_REQUIRE(n_queries >= 1, "n_queries must be >= 1");
     OSK_REQUIRE(cap >= 1, "cap must be >= 1");
-    int32_t rc = any_device();
+    int32_t rc = refuse_hamming(view->sim, "similarity-threshold search");
+    if (rc) return rc;
+    rc = any_device();
     if (rc) return rc;
     rc = check_device(view->device);
     if (rc) return rc;
@@ -2360,6 +2375,7 @@ int32_t osk_view_search_nested_device(osk_view* view, const void* d_queries, int
     OSK_REQUIRE(d_queries && d_shard_keys && d_shard_counts, "null device buffer");
     int32_t rc = nested_args(n_queries, k);
     if (rc) return rc;
+    if ((rc = refuse_hamming(view->sim, "nested search")) != OSK_OK) return rc;
     rc = any_device();
     if (rc) return rc;
     rc = check_device(view->device);
@@ -3052,7 +3068,9 @@ int32_t osk_view_search_threshold(osk_view* view, const void* queries, int32_t n
     OSK_REQUIRE(out_docs && out_scores && out_count && out_total, "null output");
     OSK_REQUIRE(n_queries >= 1, "n_queries must be >= 1");
     OSK_REQUIRE(cap >= 1, "cap must be >= 1");
-    int32_t rc = any_device();
+    int32_t rc = refuse_hamming(view->sim, "similarity-threshold search");
+    if (rc) return rc;
+    rc = any_device();
     if (rc) return rc;
     rc = check_device(view->device);
     if (rc) return rc;
@@ -3070,7 +3088,9 @@ int32_t osk_seg_search_threshold(osk_seg* seg, const void* queries, int32_t n_qu
     OSK_REQUIRE(out_docs && out_scores && out_count && out_total, "null output");
     OSK_REQUIRE(n_queries >= 1, "n_queries must be >= 1");
     OSK_REQUIRE(cap >= 1, "cap must be >= 1");
-    int32_t rc = any_device();
+    int32_t rc = refuse_hamming(seg->sim, "similarity-threshold search");
+    if (rc) return rc;
+    rc = any_device();
     if (rc) return rc;
     rc = check_device(seg->device);
     if (rc) return rc;
@@ -3102,6 +3122,7 @@ int32_t osk_view_search_nested(osk_view* view, const void* queries, int32_t n_qu
     OSK_REQUIRE(from >= 0 && size >= 1, "bad from/size");
     int32_t rc = nested_args(n_queries, k);
     if (rc) return rc;
+    if ((rc = refuse_hamming(view->sim, "nested search")) != OSK_OK) return rc;
     rc = any_device();
     if (rc) return rc;
     return view_search_host(view, queries, n_queries, k, from, size, accept, out_scores, out_docs, out_shard_index,
@@ -3118,6 +3139,7 @@ int32_t osk_seg_search_nested(osk_seg* seg, const void* queries, int32_t n_queri
     OSK_REQUIRE(out_scores && out_docs && out_count, "null output");
     int32_t rc = nested_args(n_queries, k);
     if (rc) return rc;
+    if ((rc = refuse_hamming(seg->sim, "nested search")) != OSK_OK) return rc;
     rc = any_device();
     if (rc) return rc;
     return seg_search_host(seg, queries, n_queries, k, accept_bits, out_scores, out_docs, out_count, out_visited,

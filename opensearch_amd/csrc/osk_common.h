@@ -62,6 +62,8 @@ OSK_HD int32_t key_doc(uint64_t key) { return (int32_t)(0xFFFFFFFFu - (uint32_t)
 //   byte MAX_INNER_PRODUCT scaleMaxInnerProductScore((float)dot_int)
 // ---------------------------------------------------------------------------------------------
 enum { SIM_EUCLIDEAN = 0, SIM_DOT_PRODUCT = 1, SIM_COSINE = 2, SIM_MIP = 3 };
+// Not a Lucene ordinal: packed-bit byte fields (osknn.h OSK_HAMMING), scored by score_hamming below.
+enum { SIM_HAMMING = 4 };
 enum { ENC_FLOAT32 = 0, ENC_BYTE = 1 };
 
 OSK_HD float java_max0(float v) { return v >= 0.0f ? v : (v != v ? v : 0.0f); }
@@ -95,6 +97,9 @@ OSK_HD float score_i8(int sim, int32_t s, int32_t qn, int32_t xn, int dim) {
         default: return mip_scale((float)s);
     }
 }
+// packed bits: `d` = popcount(q XOR x), exact.  OpenSearch k-NN's translation of the Hamming space, with the
+// float operations of score_i8's EUCLIDEAN case (so the score of distance d is that case's score of d² = d).
+OSK_HD float score_hamming(int32_t d) { return 1.0f / (1.0f + (float)d); }
 
 // ---------------------------------------------------------------------------------------------
 // Lane layout (defines the fp32 summation order).  A row of n4 float4s

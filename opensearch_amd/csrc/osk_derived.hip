@@ -94,7 +94,8 @@ int32_t seg_finish(osk_seg* s, const int32_t* ord_to_doc, hipStream_t st) {
             OSK_HIP(launch_row_norms_f32(s->d_rows.as<const float4>(), s->n_rows, s->units, s->cfg,
                                          xnorm_f.as<float>(), st));
     }
-    if (s->enc == ENC_BYTE) {
+    // (a Hamming segment keeps no Σx²: its kernels have no use for it, and 4 B per row is a quarter of a 128-bit row)
+    if (s->enc == ENC_BYTE && s->sim != SIM_HAMMING) {
         OSK_HIP(xnorm_i.reserve(n * sizeof(int32_t)));
         if (s->n_rows > 0)
             OSK_HIP(launch_row_norms_i8(s->d_rows.as<const int4>(), s->n_rows, s->units, xnorm_i.as<int32_t>(), st));
@@ -127,7 +128,9 @@ int32_t seg_alloc(int device, int64_t n_rows, int dim, int enc, int sim, int max
     OSK_REQUIRE(n_rows >= 0, "n_rows must be >= 0");
     OSK_REQUIRE(dim >= 1 && dim <= OSK_MAX_DIM, "dim must be in [1, 4096]");
     OSK_REQUIRE(enc == ENC_FLOAT32 || enc == ENC_BYTE, "unknown encoding");
-    OSK_REQUIRE(sim >= 0 && sim <= 3, "unknown similarity");
+    OSK_REQUIRE(sim >= 0 && sim <= SIM_HAMMING, "unknown similarity");
+    OSK_REQUIRE(sim != SIM_HAMMING || enc == ENC_BYTE,
+                "hamming similarity needs a byte field: OSK_HAMMING is served for OSK_BYTE (packed bits) only");
     OSK_REQUIRE(n_rows <= 0x7FFFFFFFll, "a Lucene segment holds < 2^31 docs");
     if (ord_to_doc == nullptr) OSK_REQUIRE(max_doc >= n_rows, "max_doc < n_rows for a dense field");
     int32_t rc = check_device(device);

@@ -556,6 +556,7 @@ struct Tuning {
                                           // first and scan them (osk_filter.hip); 0 = walk the bitset windows
     std::atomic<int> sq8_mfma_nt{1};      // A/B: non-temporal row loads in sq8_mfma
     std::atomic<int> i8_stream{1};        // byte fields, one query, no filter: scan_i8_stream (0 = scan_i8)
+    std::atomic<int> ham_stream{1};       // Hamming fields, one query, no filter: scan_ham_stream (0 = scan_ham)
     std::atomic<int> call_timing{0};      // host entries time each call on the device (osk_last_call_device_ns)
     std::atomic<int> sq8_mfma_ring{-1};   // sq8_mfma LDS-DMA ring slots per wave (≤ 256 dims, unfiltered):
                                           // -1 = as many as fit 2 workgroups per CU, 0 = off (register loads)
@@ -608,6 +609,20 @@ extern Tuning g_tuning;
 
 hipError_t launch_scan(int enc, int cfg, int nq, const ScanParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
                        hipEvent_t ev_stop = nullptr);
+
+// ---- packed bits, Hamming distance (osk_hamming.hip): SIM_HAMMING views ----
+// The scans take the streaming scan's parameters plus the stride between the launch's padded queries: the
+// kernels' lane configs are their own (by the row's units), not the kCfgLV row the queries were padded for.
+struct HamParams : ScanParams {
+    int q_units;                     // 16-B units between consecutive queries at `q` (≥ units, zero padded)
+};
+// scan_ham (≤ kMaxNQ queries, filters) or, for one unfiltered query with tune ham_stream on, scan_ham_stream;
+// k ≤ kScanMaxK.  Checks its arguments and returns hipErrorInvalidValue instead of launching.
+hipError_t launch_scan_ham(int nq, const HamParams& p, hipStream_t s, hipEvent_t ev_start = nullptr,
+                           hipEvent_t ev_stop = nullptr);
+// the select path's exact key writer of a Hamming view (sel_keys_ham) for rows of `units` units
+using SelKeysFn = void (*)(SelParams);
+SelKeysFn sel_keys_ham_fn(int units);
 
 // ---- similarity-threshold search (osk_threshold.hip): every accepted row with score ≥ min_score ----
 // One corpus pass (thr_scan_*: hit mask words + hit counts per (query, tile, wave)), a prefix sum per

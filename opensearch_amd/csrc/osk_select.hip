@@ -828,9 +828,11 @@ hipError_t launch_select_one(const SelParams& p, int cfg, hipStream_t s, hipEven
     const dim3 tg(p.n_tiles), tb(kSelThreads);
     hipLaunchKernelGGL(sel_init, dim3(p.n_shards * kSelRep), dim3(256), 0, s, p);
     // the writer (stamped by the profile events when given)
-    SelFn writer = p.exact ? (p.enc == ENC_BYTE ? kSelKeysI8[sel_bounds_cfg(p.units)]
-                                                : kSelKeysF32[cfg][p.sim == SIM_EUCLIDEAN ? 1 : 0])
+    SelFn writer = p.exact ? (p.sim == SIM_HAMMING ? sel_keys_ham_fn(p.units)
+                              : p.enc == ENC_BYTE  ? kSelKeysI8[sel_bounds_cfg(p.units)]
+                                                   : kSelKeysF32[cfg][p.sim == SIM_EUCLIDEAN ? 1 : 0])
                            : kSelBounds[sel_bounds_cfg(p.units8)][p.writer & 3][p.accept ? 1 : 0];
+    if (!writer || (p.sim == SIM_HAMMING && !p.exact)) return hipErrorInvalidValue;
     if (ev_start || ev_stop)
         hipExtLaunchKernelGGL(writer, tg, tb, 0, s, ev_start, ev_stop, 0, p);
     else

@@ -10,6 +10,9 @@ plugin's public request format so existing requests keep working:
   mapping  {"type": "knn_vector", "dimension": 768, "data_type": "float" | "byte",
             "space_type": "l2" | "innerproduct" | "cosinesimil" | "dot_product",
             "method": {"name": "flat", "engine": "gpu"}}                     (method optional)
+           {"type": "knn_vector", "dimension": 768, "data_type": "binary", "space_type": "hamming"}
+           (packed bits: dimension in bits, a multiple of 8; vectors are dimension / 8 integers in [-128, 127];
+           space_type defaults to hamming and no other pairs with binary; k-NN only — no min_score, no nested)
   query    {"knn": {"<field>": {"vector": [...], "k": 10, "filter": <query>}}}
            {"knn": {"<field>": {"vector": [...], "min_score": 0.8, "filter": <query>}}}   (radial search:
            every document scoring at least min_score; exactly one of k / min_score)
@@ -36,7 +39,7 @@ from typing import Any, Callable
 
 import numpy as np
 
-from .lucene import (ByteVectorSimilarityQuery, DiversifyingChildrenByteKnnVectorQuery,
+from .lucene import (BinarySimilarity, ByteVectorSimilarityQuery, DiversifyingChildrenByteKnnVectorQuery,
                      DiversifyingChildrenFloatKnnVectorQuery, FloatVectorSimilarityQuery, KnnByteVectorQuery,
                      KnnFloatVectorQuery, VectorEncoding, VectorSimilarityFunction)
 
@@ -48,8 +51,12 @@ SPACE_TYPES = {
     "innerproduct": VectorSimilarityFunction.MAXIMUM_INNER_PRODUCT,
     "cosinesimil": VectorSimilarityFunction.COSINE,
     "dot_product": VectorSimilarityFunction.DOT_PRODUCT,
+    "hamming": BinarySimilarity.HAMMING,          # with data_type binary only (and its default)
 }
-DATA_TYPES = {"float": VectorEncoding.FLOAT32, "byte": VectorEncoding.BYTE}
+# binary: packed bits, `dimension` in bits (a multiple of 8), dimension / 8 integers in [-128, 127] per vector
+DATA_TYPES = {"float": VectorEncoding.FLOAT32, "byte": VectorEncoding.BYTE, "binary": VectorEncoding.BYTE}
+BINARY_DATA_TYPE = "binary"
+HAMMING_SPACE_TYPE = "hamming"
 
 
 class MapperParsingException(ValueError):
@@ -73,10 +80,20 @@ class KnnVectorFieldType:
     name: str
     dimension: int
     encoding: VectorEncoding
-    similarity: VectorSimilarityFunction
+    similarity: VectorSimilarityFunction | BinarySimilarity
     space_type: str
     data_type: str
     method: dict = field(default_factory=dict, compare=False)
+
+    @property
+    def binary(self) -> bool:
+        return self.data_type == BINARY_DATA_TYPE
+
+    @property
+    def vector_length(self) -> int:
+        """Elements per document / query vector, which is the reader's `dim`: `dimension`, or for a binary
+        field (dimension in bits) the dimension / 8 bytes."""
+        return self.dimension // 8 if self.binary else self.dimension
 
     def to_xcontent(self) -> dict:
         out = {"type": "knn_vector", "dimension": self.dimension, "data_type": self.data_type,
@@ -95,14 +112,23 @@ def parse_knn_vector_mapping(name: str, node: dict) -> KnnVectorFieldType:
     if "dimension" not in node:
         raise MapperParsingException(f"Dimension value missing for vector: {name}")
     dim = node.pop("dimension")
-    if not isinstance(dim, int) or isinstance(dim, bool) or not 1 <= dim <= MAX_DIMENSION:
-        raise MapperParsingException(f"Dimension value must be an integer in [1, {MAX_DIMENSION}] for vector: {name}")
     data_type = node.pop("data_type", "float")
     if data_type not in DATA_TYPES:
         raise MapperParsingException(f"[data_type] must be one of {sorted(DATA_TYPES)} for vector: {name}")
-    space = node.pop("space_type", "l2")
+    binary = data_type == BINARY_DATA_TYPE
+    if binary:   # dimension counts bits; the field holds dimension / 8 bytes
+        if (not isinstance(dim, int) or isinstance(dim, bool) or not 8 <= dim <= 8 * MAX_DIMENSION or dim % 8):
+            raise MapperParsingException(f"Dimension value must be a multiple of 8 in [8, {8 * MAX_DIMENSION}] "
+                                         f"for a [data_type] binary vector: {name}")
+    elif not isinstance(dim, int) or isinstance(dim, bool) or not 1 <= dim <= MAX_DIMENSION:
+        raise MapperParsingException(f"Dimension value must be an integer in [1, {MAX_DIMENSION}] for vector: {name}")
+    space = node.pop("space_type", HAMMING_SPACE_TYPE if binary else "l2")
     if space not in SPACE_TYPES:
         raise MapperParsingException(f"[space_type] must be one of {sorted(SPACE_TYPES)} for vector: {name}")
+    if binary != (space == HAMMING_SPACE_TYPE):
+        raise MapperParsingException(f"[space_type] {HAMMING_SPACE_TYPE} and [data_type] {BINARY_DATA_TYPE} go "
+                                     f"together only: got [space_type] {space} with [data_type] {data_type} "
+                                     f"for vector: {name}")
     method = node.pop("method", {})
     if method and (method.get("name", "flat") != "flat" or method.get("engine", "gpu") != "gpu"):
         raise MapperParsingException(f"only exact search is served: method {{name: flat, engine: gpu}} ({name})")
@@ -114,13 +140,13 @@ def parse_knn_vector_mapping(name: str, node: dict) -> KnnVectorFieldType:
 def parse_document_vector(ft: KnnVectorFieldType, value) -> np.ndarray:
     """A document's vector as the mapper indexes it (KnnFloatVectorField / KnnByteVectorField [L])."""
     arr = np.asarray(value, dtype=np.float64)
-    if arr.ndim != 1 or len(arr) != ft.dimension:
-        raise MapperParsingException(f"Vector dimension mismatch. Expected: {ft.dimension}, Given: {arr.size}")
+    if arr.ndim != 1 or len(arr) != ft.vector_length:   # (binary: dimension / 8 packed bytes)
+        raise MapperParsingException(f"Vector dimension mismatch. Expected: {ft.vector_length}, Given: {arr.size}")
     if not np.all(np.isfinite(arr)):
         raise MapperParsingException("KNN vector values cannot be NaN or Infinity")
     if ft.encoding == VectorEncoding.BYTE:
         if np.any(arr != np.round(arr)) or np.any(arr < -128) or np.any(arr > 127):
-            raise MapperParsingException("[data_type] byte requires integers in [-128, 127]")
+            raise MapperParsingException(f"[data_type] {ft.data_type} requires integers in [-128, 127]")
         return arr.astype(np.int8)
     return arr.astype(np.float32)
 
@@ -314,10 +340,14 @@ class KnnQueryBuilder:
         ft = ctx.field_type(self.field_name)
         if not isinstance(ft, KnnVectorFieldType):
             raise QueryShardException(f"Field '{self.field_name}' is not knn_vector type.")
-        target = parse_document_vector(ft, self.vector) if len(self.vector) == ft.dimension else None
+        target = parse_document_vector(ft, self.vector) if len(self.vector) == ft.vector_length else None
         if target is None:
             raise QueryShardException(f"Query vector has invalid dimension: {len(self.vector)}. "
-                                      f"Dimension should be: {ft.dimension}")
+                                      f"Dimension should be: {ft.vector_length}")
+        if ft.binary and (self.min_score is not None or ctx.parent_filter is not None):
+            # (libosknn refuses both for OSK_HAMMING: only k-NN is built for packed bits)
+            raise QueryShardException(f"[knn] {'radial (min_score)' if self.min_score is not None else 'nested'} "
+                                      f"search is not served for binary fields: [{self.field_name}]")
         filt = None
         if self.filter is not None:
             if ctx.doc_values is None:

@@ -432,12 +432,14 @@ def ord_to_doc(vec_path: str, entry: FieldEntry, max_doc: int) -> np.ndarray | N
     return docs
 
 
-def stage_field(vec_path: str, entry: FieldEntry, max_doc: int, device: int = 0) -> int:
+def stage_field(vec_path: str, entry: FieldEntry, max_doc: int, device: int = 0, similarity: int | None = None) -> int:
     """osk_seg_stage_file of one field: the .vec slice mmapped, staged through pinned buffers into HBM.
-    Returns the osk_seg handle."""
+    Returns the osk_seg handle.  `similarity` overrides the entry's (a .vemf entry can only carry a Lucene
+    ordinal: a byte field of packed bits is staged with similarity=_lib.OSK_HAMMING); None = the entry's."""
     from ._lib import check, lib, ptr
     o2d = ord_to_doc(vec_path, entry, max_doc)
     h = C.c_void_p()
+    sim = entry.similarity if similarity is None else int(similarity)
     check(lib().osk_seg_stage_file(device, vec_path.encode(), entry.data_offset, entry.size, entry.dim, entry.encoding,
-                                   entry.similarity, ptr(o2d), max_doc, C.byref(h)))
+                                   sim, ptr(o2d), max_doc, C.byref(h)))
     return h.value

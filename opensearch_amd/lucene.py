@@ -36,6 +36,19 @@ class VectorSimilarityFunction(enum.IntEnum):
     MAXIMUM_INNER_PRODUCT = 3
 
 
+class BinarySimilarity(enum.IntEnum):
+    """The similarity of a packed-bit byte field (osknn.h OSK_HAMMING): not a Lucene ordinal, so it is no member
+    of VectorSimilarityFunction.  score = 1 / (1 + popcount(q XOR x)), OpenSearch k-NN's Hamming translation."""
+    HAMMING = _lib.OSK_HAMMING
+
+
+def _as_similarity(similarity):
+    """A reader's similarity: a Lucene ordinal, or BinarySimilarity.HAMMING."""
+    if isinstance(similarity, BinarySimilarity) or int(similarity) == int(BinarySimilarity.HAMMING):
+        return BinarySimilarity(int(similarity))
+    return VectorSimilarityFunction(similarity)
+
+
 class VectorEncoding(enum.IntEnum):
     """[L] org.apache.lucene.index.VectorEncoding."""
     FLOAT32 = 0
@@ -143,7 +156,7 @@ class GpuFlatVectorsReader:
                  max_doc: int | None = None, device: int = 0, _handle: int | None = None,
                  _dim: int | None = None, _n: int | None = None):
         self.field = field
-        self.similarity = VectorSimilarityFunction(similarity)
+        self.similarity = _as_similarity(similarity)
         self.encoding = VectorEncoding(encoding)
         self.device = device
         self._h = C.c_void_p(None)
@@ -179,10 +192,12 @@ class GpuFlatVectorsReader:
 
     @classmethod
     def from_files(cls, field: str, directory: str, segment: str, segment_id: bytes, max_doc: int,
-                   field_number: int, suffix: str = "", device: int = 0):
+                   field_number: int, suffix: str = "", device: int = 0, similarity=None):
         """The reader a `KnnVectorsFormat.fieldsReader(SegmentReadState)` builds when the segment opens:
         the field's entry parsed from `segment.vemf`, its `.vec` slice staged into HBM
-        (flatfiles.stage_field → osk_seg_stage_file)."""
+        (flatfiles.stage_field → osk_seg_stage_file).  `similarity` overrides the entry's: a byte field of
+        packed bits, which Lucene can only write under one of its own ordinals, is staged with
+        BinarySimilarity.HAMMING (None = the entry's)."""
         import os
         from . import flatfiles as FF
         base = segment + (f"_{suffix}" if suffix else "")
@@ -192,8 +207,12 @@ class GpuFlatVectorsReader:
         if field_number not in entries:
             raise ValueError(f"field {field_number} has no vectors in {vemf}")
         e = entries[field_number]
-        h = FF.stage_field(vec, e, max_doc, device)
-        r = cls(field, None, VectorSimilarityFunction(e.similarity), VectorEncoding(e.encoding), max_doc=max_doc,
+        sim = _as_similarity(e.similarity if similarity is None else similarity)
+        h = FF.stage_field(vec, e, max_doc, device, None if similarity is None else int(sim))
+        if isinstance(sim, BinarySimilarity):
+            return GpuBinaryVectorsReader(field, None, max_doc=max_doc, device=device, _handle=h, _dim=e.dim,
+                                          _n=e.size)
+        r = cls(field, None, sim, VectorEncoding(e.encoding), max_doc=max_doc,
                 device=device, _handle=h, _dim=e.dim, _n=e.size)
         return r
 
@@ -288,6 +307,51 @@ class GpuFlatVectorsReader:
             self.close()
         except Exception:
             pass
+
+
+class GpuBinaryVectorsReader(GpuFlatVectorsReader):
+    """A segment's binary vector field (OpenSearch k-NN `data_type: binary`, `space_type: hamming`): packed
+    bits, `dim` BYTES per vector (8·dim bits), encoding BYTE, similarity BinarySimilarity.HAMMING.  `vectors`
+    is int8 or uint8 [n, dim_bytes] (the same bits either way).  search / search_batch and the k-NN queries
+    work as on any byte reader, targets being dim_bytes integers; search_threshold and search_nested raise
+    OskError(OSK_ERR_UNSUPPORTED): radial and nested Hamming search are not served."""
+
+    def __init__(self, field: str, vectors, ord_to_doc=None, max_doc: int | None = None, device: int = 0,
+                 _handle: int | None = None, _dim: int | None = None, _n: int | None = None):
+        if vectors is not None:
+            vectors = self.packed_bytes(vectors)
+        super().__init__(field, vectors, BinarySimilarity.HAMMING, VectorEncoding.BYTE, ord_to_doc=ord_to_doc,
+                         max_doc=max_doc, device=device, _handle=_handle, _dim=_dim, _n=_n)
+
+    @staticmethod
+    def packed_bytes(a) -> np.ndarray:
+        """int8 or uint8 packed bits → the int8 array the C-ABI takes (bit patterns unchanged)."""
+        a = np.asarray(a)
+        if a.dtype == np.uint8:
+            return np.ascontiguousarray(a).view(np.int8)
+        if a.dtype != np.int8:
+            raise ValueError(f"binary vectors are int8 or uint8 packed bits, not {a.dtype}")
+        return np.ascontiguousarray(a)
+
+    @classmethod
+    def synthetic(cls, field: str, n: int, dim_bytes: int, seed: int = 42, row0: int = 0, device: int = 0):
+        """A dense segment of uniform random bits generated on the device (DIST_INT8: synth_host's bytes)."""
+        h = C.c_void_p(None)
+        check(lib().osk_seg_synth(device, n, dim_bytes, int(VectorEncoding.BYTE), int(BinarySimilarity.HAMMING),
+                                  seed, _lib.DIST_INT8, row0, C.byref(h)))
+        return cls(field, None, device=device, _handle=h.value, _dim=dim_bytes, _n=n)
+
+    @classmethod
+    def from_files(cls, field: str, directory: str, segment: str, segment_id: bytes, max_doc: int,
+                   field_number: int, suffix: str = "", device: int = 0, similarity=None):
+        """A byte field written by Lucene (under any of its ordinals), staged as packed bits."""
+        return GpuFlatVectorsReader.from_files.__func__(GpuFlatVectorsReader, field, directory, segment, segment_id,
+                                                        max_doc, field_number, suffix, device,
+                                                        BinarySimilarity.HAMMING)
+
+    def search_batch(self, targets, k: int, accept_bits: np.ndarray | None = None):
+        t = np.asarray(targets)
+        return super().search_batch(t.view(np.int8) if t.dtype == np.uint8 else targets, k, accept_bits)
 
 
 @dataclass
