@@ -53,6 +53,10 @@
  *       [L] AbstractVectorSimilarityQuery (FloatVectorSimilarityQuery, ByteVectorSimilarityQuery) over a
  *       flat field: every accepted doc whose score is ≥ resultSimilarity, in doc order, with the exact
  *       count — OpenSearch's k-NN `min_score`.
+ *   osk_seg_search_threshold_top / osk_view_search_threshold_top / osk_view_search_threshold_top_device
+ *       The same query as the shard collects it: a TopScoreDocCollector over its scorer — the best from+size
+ *       matches by (score desc, doc asc) and totalHits = every match
+ *       (S/search/query/TopDocsCollectorContext.java:866-891) — in one call, in the k-NN entries' key layout.
  *   osk_seg_set_parents / osk_seg_search_nested / osk_view_search_nested / osk_view_search_nested_device
  *       [L] DiversifyingChildrenFloatKnnVectorQuery / DiversifyingChildrenByteKnnVectorQuery (exactSearch)
  *       with the leaf's parent BitSetProducer: the k best parents, each represented by its best accepted
@@ -343,11 +347,13 @@ int32_t osk_view_stats(osk_view* view, int64_t* batched_calls, int64_t* fallback
  * "sq8_fallback_queries" (queries where some tile's candidate
  * list overflowed past the certificate and the tile was re-scanned exactly), "sq8_exact_tiles"
  * (such tiles), "sq8_rescored_rows" (rows re-scored exactly, all calls), "select_calls" (searches
- * on the select path, k > 12), "threshold_calls" (similarity-threshold searches), "threshold_sq8_calls" (those
- * that took the int8 first pass, knob "thr_sq8"), "threshold_sq8_settled_rows" (rows it left undecided and the
- * settle re-scored exactly, all calls), "nested_calls" (nested k-NN searches), "nested_sq8_calls" (those that
- * took the int8 first pass, knob "nest_sq8"), "nested_sq8_settled_rows" (rows its settle re-scored exactly, all
- * calls), "host_slots" (workspace slots the host entries have leased: 1 + replicas),
+ * on the select path, k > 12), "threshold_calls" (similarity-threshold searches through the positional
+ * entries osk_*_search_threshold alone), "threshold_top_calls" (calls of the osk_*_search_threshold_top
+ * entries), "threshold_top_select_calls" (those of them with k > 64), "threshold_sq8_calls" (threshold
+ * searches of either kind that took the int8 first pass, knob "thr_sq8"), "threshold_sq8_settled_rows" (rows
+ * that pass left undecided and the settle re-scored exactly, all calls of either kind), "nested_calls" (nested
+ * k-NN searches), "nested_sq8_calls" (those that took the int8 first pass, knob "nest_sq8"),
+ * "nested_sq8_settled_rows" (rows its settle re-scored exactly, all calls), "host_slots" (workspace slots the host entries have leased: 1 + replicas),
  * "host_batches" / "host_batched_requests" (opportunistic batching of concurrent host calls).  The
  * search counters sum over the view and the replica slots its host entries leased.  osk_view_profile /
  * osk_view_scan_time time the device-entry calls on this view object only (per-call host timing:
@@ -432,6 +438,57 @@ int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, 
                                          const float* d_min_scores, const uint64_t* const* d_accept,
                                          int32_t cap, int32_t* d_docs, float* d_scores, int32_t* d_count,
                                          int64_t* d_total, int64_t* d_visited, void* stream);
+
+/* ---- radial search, the best hits by score: each shard's top k matches and the exact total ----
+ * What the shard does with a similarity query in the end: a TopScoreDocCollector over the query's scorer keeps
+ * numDocs = from+size hits by (score desc, doc asc) and counts every match
+ * (S/search/query/TopDocsCollectorContext.java:866-891), and the coordinator merges the shards' lists
+ * (S/action/search/SearchPhaseController.java:224-246, [L] TopDocs.merge).  These entries answer that in one
+ * call: the threshold entries' first pass decides the matches, and instead of every match by position they
+ * return each shard's best k in the k-NN entries' layout, with the exact number of matches beside it.
+ *   matching   exactly as osk_*_search_threshold above: a row matches iff it is accepted and
+ *              `score >= min_score` as an IEEE float comparison; NaN on either side never matches.
+ *   order      per shard the best k matches by score descending, then doc ascending (the hit keys' order);
+ *              scores bit-identical to every other entry's for the same row.
+ *   layout     the k-NN entries': host lists padded with -inf / INT32_MAX, device lists with key 0.
+ *   count      min(total, k) per (query, shard); total is exact whatever k is; visited as in the threshold
+ *              entries (accepted vectors scored, NaN rows included).
+ *   k          1 ≤ k ≤ OSK_MAX_K.  k ≤ 64 keeps wave lists as the streaming scan does; a larger k goes through
+ *              the select path's radix select and sort.
+ * A null pointer, n_queries < 1, k < 1, k > OSK_MAX_K, from < 0 or size < 1 is OSK_ERR_INVALID before the
+ * device is touched; a Hamming segment or view returns OSK_ERR_UNSUPPORTED; without a device the entries
+ * return OSK_ERR_NO_DEVICE.  Float32 views take the certified int8 first pass under the threshold entries'
+ * rule (knob "thr_sq8"). */
+
+/* ONE leaf: osk_seg_search's output layout (docs segment-local) plus the exact total.
+ *   out_scores/out_docs  n_queries × k;  out_count[q] = min(total, k);  out_total[q] exact
+ *   out_visited          (optional) n_queries */
+int32_t osk_seg_search_threshold_top(osk_seg* seg, const void* queries, int32_t n_queries,
+                                     const float* min_scores, int32_t k, const uint64_t* accept_bits,
+                                     float* out_scores, int32_t* out_docs, int32_t* out_count,
+                                     int64_t* out_total, int64_t* out_visited);
+/* Per shard of a view, then the coordinator reduce (from, size) over the shard lists: osk_view_search's
+ * arguments and output layout, with one threshold per query.
+ *   out_total_hits[q]  Σ over shards of the exact match totals ([L] TopDocsStats: Σ totalHits) — NOT the number
+ *                      of keys the lists hold
+ *   out_max_score[q]   the best match's score; NaN when nothing matches */
+int32_t osk_view_search_threshold_top(osk_view* view, const void* queries, int32_t n_queries,
+                                      const float* min_scores, int32_t k, int32_t from, int32_t size,
+                                      const uint64_t* const* accept, float* out_scores, int32_t* out_docs,
+                                      int32_t* out_shard_index, int32_t* out_count, int64_t* out_total_hits,
+                                      float* out_max_score);
+/* The per-shard part with DEVICE buffers, asynchronous on `stream`: osk_view_search_device's rules and key
+ * layout, so osk_merge_device / osk_merge_device_ranked take d_shard_keys and d_shard_counts unchanged.  Their
+ * d_total_hits then counts the hits the lists RETURNED (Σ min(total, k)); the number of matches is the caller's
+ * sum of d_shard_totals.
+ *   d_shard_keys    [n_queries][n_shards][k] u64 best first, 0 past the count
+ *   d_shard_counts  [n_queries][n_shards] min(total, k);  d_shard_totals  [n_queries][n_shards] exact
+ *   d_visited       optional out, n_segs int64 */
+int32_t osk_view_search_threshold_top_device(osk_view* view, const void* d_queries, int32_t n_queries,
+                                             const float* d_min_scores, int32_t k,
+                                             const uint64_t* const* d_accept, uint64_t* d_shard_keys,
+                                             int32_t* d_shard_counts, int64_t* d_shard_totals,
+                                             int64_t* d_visited, void* stream);
 
 /* ---- nested k-NN: the k best parents, each by its best child ----
  * [L] DiversifyingChildrenFloatKnnVectorQuery / DiversifyingChildrenByteKnnVectorQuery.exactSearch (Lucene 10.3),

@@ -98,6 +98,26 @@ final class OsKnn {
     static final MethodHandle VIEW_SEARCH_THRESHOLD_DEVICE = h("osk_view_search_threshold_device",
         FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
             ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+    // ...the best k matches by score per shard and the exact total (the shard's TopScoreDocCollector, one call)
+    // int32_t osk_seg_search_threshold_top(osk_seg* seg, const void* queries, int32_t n_queries,
+    //     const float* min_scores, int32_t k, const uint64_t* accept_bits, float* out_scores, int32_t* out_docs,
+    //     int32_t* out_count, int64_t* out_total, int64_t* out_visited)
+    static final MethodHandle SEG_SEARCH_THRESHOLD_TOP = h("osk_seg_search_threshold_top",
+        FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+            ADDRESS, ADDRESS, ADDRESS));
+    // int32_t osk_view_search_threshold_top(osk_view* view, const void* queries, int32_t n_queries,
+    //     const float* min_scores, int32_t k, int32_t from, int32_t size, const uint64_t* const* accept,
+    //     float* out_scores, int32_t* out_docs, int32_t* out_shard_index, int32_t* out_count,
+    //     int64_t* out_total_hits, float* out_max_score)
+    static final MethodHandle VIEW_SEARCH_THRESHOLD_TOP = h("osk_view_search_threshold_top",
+        FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, ADDRESS,
+            ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+    // int32_t osk_view_search_threshold_top_device(osk_view* view, const void* d_queries, int32_t n_queries,
+    //     const float* d_min_scores, int32_t k, const uint64_t* const* d_accept, uint64_t* d_shard_keys,
+    //     int32_t* d_shard_counts, int64_t* d_shard_totals, int64_t* d_visited, void* stream)
+    static final MethodHandle VIEW_SEARCH_THRESHOLD_TOP_DEVICE = h("osk_view_search_threshold_top_device",
+        FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+            ADDRESS, ADDRESS, ADDRESS));
 
     // Nested k-NN ([L] DiversifyingChildrenFloat/ByteKnnVectorQuery on a flat field; knn inside nested)
     // int32_t osk_seg_set_parents(osk_seg* seg, const uint64_t* parent_bits)

@@ -90,6 +90,9 @@ SIGNATURES = {
     "osk_seg_search_threshold": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "osk_view_search_threshold": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "osk_view_search_threshold_device": (_I32, [_P, _P, _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "osk_seg_search_threshold_top": (_I32, [_P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
+    "osk_view_search_threshold_top": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "osk_view_search_threshold_top_device": (_I32, [_P, _P, _I32, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "osk_seg_set_parents": (_I32, [_P, _P]),
     "osk_seg_parents": (_I32, [_P, _PI64]),
     "osk_seg_search_nested": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _P]),

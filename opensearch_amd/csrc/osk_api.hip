@@ -1674,15 +1674,11 @@ int32_t sq8_search(osk_view* v, const void* d_queries, int nq, int k, int UP, co
     return rc ? rc : sq8_finish(c, plan, lists);
 }
 
-// The select path (osk_select.hip): exact top-k for any k ≤ OSK_MAX_K, one query at a time.
-//   bounds = true: float32 fields through the int8 prefilter copy (bounds → threshold → candidates →
-//   exact re-score → top k); bounds = false: exact mode (exact keys → threshold → top k; float32 with the
-//   prefilter off, byte vectors).  The candidate buffer holds a whole shard, so nothing overflows and
-//   nothing waits on the host.  ws_q / ws_qnorm hold the padded queries (exact mode: the caller's
-//   launch_prep_queries; bounds mode: sq8_prep here).
-int32_t select_search(osk_view* v, const void* d_queries, int nq, int k, int UP, const uint64_t* const* d_accept,
-                      uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st,
-                      bool bounds) {
+// The select path's workspaces and the parameters every query of a call shares: the per-row records (bounds:
+// LB / UB; exact: keys), the radix state and histograms, and a candidate region of a whole shard.  *rows =
+// the view's rows (the records' length).
+int32_t select_workspace(osk_view* v, int k, const uint64_t* const* d_accept, bool bounds, SelParams& p,
+                         int64_t* rows) {
     const int S = v->n_shards;
     int64_t total = 0;
     std::vector<int64_t> shard_rows(S, 0);
@@ -1692,23 +1688,10 @@ int32_t select_search(osk_view* v, const void* d_queries, int nq, int k, int UP,
     }
     const int64_t cap = std::max<int64_t>(1, *std::max_element(shard_rows.begin(), shard_rows.end()));
     OSK_REQUIRE(cap < (1ll << 31), "a shard holds < 2^31 rows");
-    const int nq_pad = (nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;
-    int u8 = 0;
     if (bounds) {
-        int32_t rc = ensure_sq8(v, st);
-        if (rc) return rc;
-        u8 = v->units8;
-        OSK_HIP(v->ws_q8.reserve((size_t)nq_pad * u8 * 16));
-        OSK_HIP(v->ws_qc.reserve(sizeof(float4) * nq_pad));
-        OSK_HIP(v->ws_flags.reserve(sizeof(int) * nq));
-        OSK_HIP(launch_sq8_prep(v->cfg, static_cast<const float*>(d_queries), v->dim, nq, nq_pad, UP, u8,
-                                v->ws_q.as<float4>(), v->ws_qnorm.as<float>(), v->ws_q8.p, v->ws_qc.as<float4>(),
-                                v->ws_flags.as<int>(), st));
         OSK_HIP(v->ws_sel_lb.reserve(sizeof(uint32_t) * std::max<int64_t>(1, total)));
         OSK_HIP(v->ws_sel_ub.reserve(sizeof(uint32_t) * std::max<int64_t>(1, total)));
     } else {
-        if (v->enc == ENC_FLOAT32 && v->sim == SIM_COSINE)
-            OSK_HIP(launch_row_norms_f32(v->ws_q.as<float4>(), nq, UP, v->cfg, v->ws_qnorm.as<float>(), st));
         OSK_HIP(v->ws_sel_keys.reserve(sizeof(uint64_t) * std::max<int64_t>(1, total)));
     }
     OSK_HIP(v->ws_sel_state.reserve(sizeof(RadixState) * S));
@@ -1716,7 +1699,6 @@ int32_t select_search(osk_view* v, const void* d_queries, int nq, int k, int UP,
     OSK_HIP(v->ws_sel_cand.reserve(sizeof(uint64_t) * (size_t)cap * S));
     if (cap > kSelCap) OSK_HIP(v->ws_sel_cand2.reserve(sizeof(uint64_t) * (size_t)cap * S));
     OSK_HIP(v->ws_sel_cnt.reserve(sizeof(int32_t) * std::max(1, v->n_tiles)));
-    SelParams p{};
     p.segs = v->d_segs.as<SegDev>();
     p.tiles = v->d_tiles.as<TileDev>();
     p.seg_vrow = v->d_seg_vrow.as<int64_t>();
@@ -1730,14 +1712,8 @@ int32_t select_search(osk_view* v, const void* d_queries, int nq, int k, int UP,
     p.sim = v->sim;
     p.dim = v->dim;
     p.units = v->units;
-    p.units8 = u8;
     p.enc = v->enc;
     p.exact = bounds ? 0 : 1;
-    p.writer = g_tuning.sel_writer.load(std::memory_order_relaxed);
-    p.rows8 = v->d_sq8_rows.as<const int4*>();
-    p.aux = v->d_sq8_aux.as<const float4*>();
-    p.gam = v->sq8_gam;
-    p.g2 = v->sq8_g2;
     p.lb = v->ws_sel_lb.as<uint32_t>();
     p.ub = v->ws_sel_ub.as<uint32_t>();
     p.keys = v->ws_sel_keys.as<uint64_t>();
@@ -1747,6 +1723,45 @@ int32_t select_search(osk_view* v, const void* d_queries, int nq, int k, int UP,
     p.cand2 = v->ws_sel_cand2.as<uint64_t>();
     p.tile_count = v->ws_sel_cnt.as<int32_t>();
     p.cap = (int)cap;
+    if (rows) *rows = total;
+    return OSK_OK;
+}
+
+// The select path (osk_select.hip): exact top-k for any k ≤ OSK_MAX_K, one query at a time.
+//   bounds = true: float32 fields through the int8 prefilter copy (bounds → threshold → candidates →
+//   exact re-score → top k); bounds = false: exact mode (exact keys → threshold → top k; float32 with the
+//   prefilter off, byte vectors).  The candidate buffer holds a whole shard, so nothing overflows and
+//   nothing waits on the host.  ws_q / ws_qnorm hold the padded queries (exact mode: the caller's
+//   launch_prep_queries; bounds mode: sq8_prep here).
+int32_t select_search(osk_view* v, const void* d_queries, int nq, int k, int UP, const uint64_t* const* d_accept,
+                      uint64_t* d_shard_keys, int32_t* d_shard_counts, int64_t* d_visited, hipStream_t st,
+                      bool bounds) {
+    const int S = v->n_shards;
+    const int nq_pad = (nq + kMaxNQ - 1) / kMaxNQ * kMaxNQ;
+    int u8 = 0;
+    if (bounds) {
+        int32_t rc = ensure_sq8(v, st);
+        if (rc) return rc;
+        u8 = v->units8;
+        OSK_HIP(v->ws_q8.reserve((size_t)nq_pad * u8 * 16));
+        OSK_HIP(v->ws_qc.reserve(sizeof(float4) * nq_pad));
+        OSK_HIP(v->ws_flags.reserve(sizeof(int) * nq));
+        OSK_HIP(launch_sq8_prep(v->cfg, static_cast<const float*>(d_queries), v->dim, nq, nq_pad, UP, u8,
+                                v->ws_q.as<float4>(), v->ws_qnorm.as<float>(), v->ws_q8.p, v->ws_qc.as<float4>(),
+                                v->ws_flags.as<int>(), st));
+    } else {
+        if (v->enc == ENC_FLOAT32 && v->sim == SIM_COSINE)
+            OSK_HIP(launch_row_norms_f32(v->ws_q.as<float4>(), nq, UP, v->cfg, v->ws_qnorm.as<float>(), st));
+    }
+    SelParams p{};
+    const int32_t rc_ws = select_workspace(v, k, d_accept, bounds, p, nullptr);
+    if (rc_ws) return rc_ws;
+    p.units8 = u8;
+    p.writer = g_tuning.sel_writer.load(std::memory_order_relaxed);
+    p.rows8 = v->d_sq8_rows.as<const int4*>();
+    p.aux = v->d_sq8_aux.as<const float4*>();
+    p.gam = v->sq8_gam;
+    p.g2 = v->sq8_g2;
     for (int q = 0; q < nq; ++q) {
         p.q = v->ws_q.as<char>() + (size_t)q * UP * 16;
         p.qnorm = v->ws_qnorm.as<float>() + q;
@@ -1954,14 +1969,20 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k,
     return OSK_OK;
 }
 
-// Core of osk_view_search_threshold_device (caller holds the view mutex; device already set): passes of up
-// to kThrNQ queries, each one corpus read (thr_scan), a prefix sum (thr_offsets) and an in-order emit.
-int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const float* d_min_scores,
-                              const uint64_t* const* d_accept, int cap, int32_t* d_docs, float* d_scores,
-                              int32_t* d_count, int64_t* d_total, int64_t* d_visited, hipStream_t st) {
-    OSK_REQUIRE(nq >= 1, "n_queries must be >= 1");
-    OSK_REQUIRE(cap >= 1, "cap must be >= 1");
-    OSK_REQUIRE(d_queries && d_min_scores && d_docs && d_scores && d_count && d_total, "null device buffer");
+// What the two threshold cores (every hit by position; the best k by score) share: the query prep, the mask /
+// maybe / counts / offsets workspaces, the parameters of a pass and its first-pass launches.  The cores
+// differ only in what follows thr_offsets.
+namespace {
+struct ThrCall {
+    ThrParams p{};
+    bool use8 = false;   // the certified int8 first pass (thr_scan_sq8 + thr_settle_f32)
+    int UP = 0;
+    size_t waves = 0;    // per query of a pass
+};
+
+// The prep of a call of nq queries; c.p is complete but for the outputs and the per-pass fields.
+int32_t thr_begin(osk_view* v, const void* d_queries, int nq, const uint64_t* const* d_accept, int64_t* d_visited,
+                  hipStream_t st, ThrCall& c) {
     int32_t rc = order_after_last(v, st);
     if (rc) return rc;
     const int UP = cfg_padded_units(v->cfg);
@@ -1997,7 +2018,10 @@ int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const 
     if (d_visited) OSK_HIP(hipMemsetAsync(d_visited, 0, sizeof(int64_t) * v->segs.size(), st));
     if ((rc = profile_sample(v, st, false)) != OSK_OK) return rc;
 
-    ThrParams p{};
+    c.use8 = use8;
+    c.UP = UP;
+    c.waves = waves;
+    ThrParams& p = c.p;
     if (use8) {
         p.maybe = v->ws_thr_maybe.as<uint64_t>();
         p.rows8 = v->d_sq8_rows.as<const int4*>();
@@ -2017,43 +2041,133 @@ int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const 
     p.offsets = v->ws_thr_offsets.as<int64_t>();
     p.visited = reinterpret_cast<unsigned long long*>(d_visited);
     p.shard_tile_begin = v->d_shard_tile_begin.as<int32_t>();
-    p.out_docs = d_docs;
-    p.out_scores = d_scores;
-    p.out_count = d_count;
-    p.out_total = d_total;
     p.n_tiles = v->n_tiles;
     p.n_shards = v->n_shards;
     p.wpw = wpw;
     p.units = v->units;
     p.sim = v->sim;
     p.dim = v->dim;
+    return OSK_OK;
+}
+
+// The pass of the call's queries [q0, q0 + kThrNQ): its fields of c.p, and (with tiles) the cleared mask and the
+// corpus read that fills it and the counts.  What follows — thr_offsets and the emit or the collector — is the
+// caller's.
+int32_t thr_first_pass(osk_view* v, ThrCall& c, int q0, int nq, const float* d_min_scores, hipStream_t st) {
+    ThrParams& p = c.p;
+    p.q0 = q0;
+    p.q_count = std::min(kThrNQ, nq - q0);
+    p.q = v->ws_q.as<char>() + (size_t)q0 * c.UP * 16;
+    p.min_score = d_min_scores + q0;
+    if (v->n_tiles <= 0) return OSK_OK;   // (nothing staged: thr_offsets alone writes zero hits for every shard)
+    OSK_HIP(hipMemsetAsync(p.mask, 0, sizeof(uint64_t) * p.q_count * c.waves * p.wpw, st));
+    hipEvent_t ev_stop = v->profile && q0 + kThrNQ >= nq ? v->ev1 : nullptr;
+    if (c.use8) {
+        OSK_HIP(hipMemsetAsync(p.maybe, 0, sizeof(uint64_t) * p.q_count * c.waves * p.wpw, st));
+        p.q8 = v->ws_q8.as<int4>() + (size_t)q0 * v->units8;
+        p.qc = v->ws_qc.as<float4>() + q0;
+        p.qnorm = v->ws_qnorm.as<float>() + q0;
+        p.qflags = v->ws_flags.as<int>() + q0;
+        OSK_HIP(launch_thr_scan_sq8(v->cfg, p, st, launch_ev_start(v, q0), ev_stop));
+        OSK_HIP(launch_thr_settle(v->cfg, p, st));
+    } else {
+        OSK_HIP(launch_thr_scan(v->enc, v->cfg, p, st, launch_ev_start(v, q0), ev_stop));
+    }
+    return OSK_OK;
+}
+}  // namespace
+
+// Core of osk_view_search_threshold_device (caller holds the view mutex; device already set): passes of up
+// to kThrNQ queries, each one corpus read (thr_scan), a prefix sum (thr_offsets) and an in-order emit.
+int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const float* d_min_scores,
+                              const uint64_t* const* d_accept, int cap, int32_t* d_docs, float* d_scores,
+                              int32_t* d_count, int64_t* d_total, int64_t* d_visited, hipStream_t st) {
+    OSK_REQUIRE(nq >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(cap >= 1, "cap must be >= 1");
+    OSK_REQUIRE(d_queries && d_min_scores && d_docs && d_scores && d_count && d_total, "null device buffer");
+    ThrCall c;
+    int32_t rc = thr_begin(v, d_queries, nq, d_accept, d_visited, st, c);
+    if (rc) return rc;
+    ThrParams& p = c.p;
+    p.out_docs = d_docs;
+    p.out_scores = d_scores;
+    p.out_count = d_count;
+    p.out_total = d_total;
     p.cap = cap;
     for (int q0 = 0; q0 < nq; q0 += kThrNQ) {
-        p.q0 = q0;
-        p.q_count = std::min(kThrNQ, nq - q0);
-        p.q = v->ws_q.as<char>() + (size_t)q0 * UP * 16;
-        p.min_score = d_min_scores + q0;
-        if (v->n_tiles > 0) {   // (nothing staged: thr_offsets alone writes zero hits for every shard)
-            OSK_HIP(hipMemsetAsync(p.mask, 0, sizeof(uint64_t) * p.q_count * waves * wpw, st));
-            hipEvent_t ev_stop = v->profile && q0 + kThrNQ >= nq ? v->ev1 : nullptr;
-            if (use8) {
-                OSK_HIP(hipMemsetAsync(p.maybe, 0, sizeof(uint64_t) * p.q_count * waves * wpw, st));
-                p.q8 = v->ws_q8.as<int4>() + (size_t)q0 * v->units8;
-                p.qc = v->ws_qc.as<float4>() + q0;
-                p.qnorm = v->ws_qnorm.as<float>() + q0;
-                p.qflags = v->ws_flags.as<int>() + q0;
-                OSK_HIP(launch_thr_scan_sq8(v->cfg, p, st, launch_ev_start(v, q0), ev_stop));
-                OSK_HIP(launch_thr_settle(v->cfg, p, st));
-            } else {
-                OSK_HIP(launch_thr_scan(v->enc, v->cfg, p, st, launch_ev_start(v, q0), ev_stop));
-            }
-        }
+        if ((rc = thr_first_pass(v, c, q0, nq, d_min_scores, st)) != OSK_OK) return rc;
         OSK_HIP(launch_thr_offsets(p, st));
         if (v->n_tiles > 0) OSK_HIP(launch_thr_emit(v->enc, v->cfg, p, st));
     }
     if (v->n_tiles > 0 && (rc = profile_end(v, st, false)) != OSK_OK) return rc;
     v->thr_calls += 1;
-    v->thr_sq8_calls += use8 ? 1 : 0;
+    v->thr_sq8_calls += c.use8 ? 1 : 0;
+    return OSK_OK;
+}
+
+// Core of osk_view_search_threshold_top_device (caller holds the view mutex; device already set): the same
+// passes up to thr_offsets, which here writes the exact totals alone; then the pass's masked rows are
+// re-scored into keys instead of positions.  k ≤ kScanMaxK: thr_top_* leaves a best-first list per (query,
+// tile) and one merge_shards after the last pass makes the shard lists.  Larger k: per query, thr_keys_*
+// stores the hit keys by view row into the select path's zeroed records and launch_select_one (keys_written)
+// selects, collects and sorts them.  At most k candidates reach sel_sort — the shard's non-zero keys when
+// they are ≤ k, else exactly the k largest (keys are distinct) — so they fit its LDS (k ≤ OSK_MAX_K < kSelCap),
+// cand2 is never read, and cand stays sized for a whole shard as the k-NN select path leaves it.
+int32_t view_threshold_top_device(osk_view* v, const void* d_queries, int nq, const float* d_min_scores, int k,
+                                  const uint64_t* const* d_accept, uint64_t* d_shard_keys,
+                                  int32_t* d_shard_counts, int64_t* d_shard_totals, int64_t* d_visited,
+                                  hipStream_t st) {
+    OSK_REQUIRE(nq >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(k >= 1 && k <= OSK_MAX_K, "k must be in [1, OSK_MAX_K]");
+    OSK_REQUIRE(d_queries && d_min_scores && d_shard_keys && d_shard_counts && d_shard_totals,
+                "null device buffer");
+    static_assert(OSK_MAX_K <= kSelCap, "the collector's candidates are sorted in LDS");
+    ThrCall c;
+    int32_t rc = thr_begin(v, d_queries, nq, d_accept, d_visited, st, c);
+    if (rc) return rc;
+    const bool select = k > kScanMaxK;
+    ThrParams& p = c.p;
+    p.out_total = d_shard_totals;
+    p.top_k = k;
+    SelParams sp{};
+    int64_t rows = 0;
+    if (v->n_tiles > 0 && select) {
+        if ((rc = select_workspace(v, k, nullptr, false, sp, &rows)) != OSK_OK) return rc;
+        sp.keys_written = 1;
+        p.top_keys = sp.keys;
+        p.seg_vrow = sp.seg_vrow;
+    } else if (v->n_tiles > 0) {
+        OSK_HIP(v->ws_cand.reserve(sizeof(uint64_t) * (size_t)nq * v->n_tiles * k));
+        p.top_cand = v->ws_cand.as<uint64_t>();
+    }
+    for (int q0 = 0; q0 < nq; q0 += kThrNQ) {
+        if ((rc = thr_first_pass(v, c, q0, nq, d_min_scores, st)) != OSK_OK) return rc;
+        OSK_HIP(launch_thr_offsets(p, st));
+        if (v->n_tiles <= 0) continue;
+        if (!select) {
+            OSK_HIP(launch_thr_top(v->enc, v->cfg, p, st));
+            continue;
+        }
+        for (int b = 0; b < p.q_count; ++b) {
+            OSK_HIP(hipMemsetAsync(sp.keys, 0, sizeof(uint64_t) * (size_t)rows, st));
+            p.key_b = b;
+            OSK_HIP(launch_thr_keys(v->enc, v->cfg, p, st));
+            sp.out_keys = d_shard_keys + (size_t)(q0 + b) * v->n_shards * k;
+            sp.out_counts = d_shard_counts + (size_t)(q0 + b) * v->n_shards;
+            OSK_HIP(launch_select_one(sp, v->cfg, st));
+        }
+    }
+    if (v->n_tiles <= 0) {
+        if ((rc = zero_shard_hits(v, nq, k, d_shard_keys, d_shard_counts, d_visited, st)) != OSK_OK) return rc;
+    } else {
+        if (!select)
+            OSK_HIP(launch_merge_shards(p.top_cand, v->n_tiles, p.shard_tile_begin, v->n_shards, nq, k, d_shard_keys,
+                                        d_shard_counts, st));
+        if ((rc = profile_end(v, st, false)) != OSK_OK) return rc;
+    }
+    v->thr_top_calls += 1;
+    v->thr_top_sel_calls += select ? 1 : 0;
+    v->thr_sq8_calls += c.use8 ? 1 : 0;
     return OSK_OK;
 }
 
@@ -2351,6 +2465,36 @@ int32_t osk_view_search_threshold_device(osk_view* view, const void* d_queries, 
     std::lock_guard<std::mutex> lk(view->mu);
     return view_threshold_device(view, d_queries, n_queries, d_min_scores, d_accept, cap, d_docs, d_scores, d_count,
                                  d_total, d_visited, st);
+    OSK_GUARD_END
+}
+
+// The argument rules every threshold top-k entry checks before the device is touched.
+static int32_t threshold_top_args(int32_t n_queries, int32_t k) {
+    OSK_REQUIRE(n_queries >= 1, "n_queries must be >= 1");
+    OSK_REQUIRE(k >= 1 && k <= OSK_MAX_K, "k must be in [1, OSK_MAX_K]");
+    return OSK_OK;
+}
+
+int32_t osk_view_search_threshold_top_device(osk_view* view, const void* d_queries, int32_t n_queries,
+                                             const float* d_min_scores, int32_t k, const uint64_t* const* d_accept,
+                                             uint64_t* d_shard_keys, int32_t* d_shard_counts,
+                                             int64_t* d_shard_totals, int64_t* d_visited, void* stream) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(view != nullptr, "view is null");
+    OSK_REQUIRE(d_queries && d_min_scores && d_shard_keys && d_shard_counts && d_shard_totals,
+                "null device buffer");
+    int32_t rc = threshold_top_args(n_queries, k);
+    if (rc) return rc;
+    if ((rc = refuse_hamming(view->sim, "similarity-threshold search")) != OSK_OK) return rc;
+    rc = any_device();
+    if (rc) return rc;
+    rc = check_device(view->device);
+    if (rc) return rc;
+    hipStream_t st = stream_or_default(stream, view->device);
+    std::lock_guard<std::mutex> lk(view->mu);
+    return view_threshold_top_device(view, d_queries, n_queries, d_min_scores, k, d_accept, d_shard_keys,
+                                     d_shard_counts, d_shard_totals, d_visited, st);
     OSK_GUARD_END
 }
 
@@ -2659,6 +2803,8 @@ int32_t osk_view_counter(osk_view* v, const char* name, int64_t* value) {
         {"sq8_wide_calls", -1, &osk_view::sq8w_calls},
         {"threshold_calls", -1, &osk_view::thr_calls},
         {"threshold_sq8_calls", -1, &osk_view::thr_sq8_calls},
+        {"threshold_top_calls", -1, &osk_view::thr_top_calls},
+        {"threshold_top_select_calls", -1, &osk_view::thr_top_sel_calls},
         {"nested_calls", -1, &osk_view::nest_calls},
         {"nested_sq8_calls", -1, &osk_view::nest_sq8_calls},
         {"sq8_fallback_queries", kCtrFallbackQueries, nullptr},
@@ -3103,6 +3249,130 @@ int32_t osk_seg_search_threshold(osk_seg* seg, const void* queries, int32_t n_qu
                         &visited);
     if (rc) return rc;
     for (int q = 0; out_visited && q < n_queries; ++q) out_visited[q] = visited;
+    return OSK_OK;
+    OSK_GUARD_END
+}
+
+// The device part of both host top-k threshold entries, on the leased slot `v` and its stream: queries, thresholds
+// and bitsets uploaded, then the core.  Leaves the shard lists in ws_keys / ws_counts, the exact totals in
+// ws_thr_tot [nq][S] and, when asked, the visited counts in ws_visited [n_segs].
+static int32_t threshold_top_shards(osk_view* v, hipStream_t st, const void* queries, int nq, const float* min_scores,
+                                    int k, const uint64_t* const* accept, bool want_visited) {
+    const int S = v->n_shards;
+    const size_t qbytes = (size_t)nq * v->dim * elem_bytes(v->enc);
+    const uint64_t* const* d_acc = nullptr;
+    int32_t rc = upload_accept(v, accept, st, &d_acc);
+    if (rc) return rc;
+    OSK_HIP(v->ws_qin.reserve(std::max<size_t>(16, qbytes)));
+    OSK_HIP(hipMemcpyAsync(v->ws_qin.p, queries, qbytes, hipMemcpyHostToDevice, st));
+    OSK_HIP(v->ws_thr_min.reserve(sizeof(float) * nq));
+    OSK_HIP(hipMemcpyAsync(v->ws_thr_min.p, min_scores, sizeof(float) * nq, hipMemcpyHostToDevice, st));
+    OSK_HIP(v->ws_keys.reserve(sizeof(uint64_t) * (size_t)nq * S * k));
+    OSK_HIP(v->ws_counts.reserve(sizeof(int32_t) * (size_t)nq * S));
+    OSK_HIP(v->ws_thr_tot.reserve(sizeof(int64_t) * (size_t)nq * S));
+    if (want_visited) OSK_HIP(v->ws_visited.reserve(sizeof(int64_t) * v->segs.size()));
+    return view_threshold_top_device(v, v->ws_qin.p, nq, v->ws_thr_min.as<float>(), k, d_acc, v->ws_keys.as<uint64_t>(),
+                                     v->ws_counts.as<int32_t>(), v->ws_thr_tot.as<int64_t>(),
+                                     want_visited ? v->ws_visited.as<int64_t>() : nullptr, st);
+}
+
+int32_t osk_view_search_threshold_top(osk_view* view, const void* queries, int32_t n_queries, const float* min_scores,
+                                      int32_t k, int32_t from, int32_t size, const uint64_t* const* accept,
+                                      float* out_scores, int32_t* out_docs, int32_t* out_shard_index,
+                                      int32_t* out_count, int64_t* out_total_hits, float* out_max_score) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(view != nullptr && queries != nullptr && min_scores != nullptr, "null argument");
+    OSK_REQUIRE(out_scores && out_docs && out_shard_index && out_count && out_total_hits && out_max_score,
+                "null output");
+    int32_t rc = threshold_top_args(n_queries, k);
+    if (rc) return rc;
+    OSK_REQUIRE(from >= 0 && size >= 1, "bad from/size");
+    if ((rc = refuse_hamming(view->sim, "similarity-threshold search")) != OSK_OK) return rc;
+    rc = any_device();
+    if (rc) return rc;
+    rc = check_device(view->device);
+    if (rc) return rc;
+    HostCall call;
+    if ((rc = call.begin(view)) != OSK_OK) return rc;
+    osk_view* v = call.v;
+    hipStream_t st = call.st;
+    const int nq = n_queries, S = v->n_shards;
+    if ((rc = threshold_top_shards(v, st, queries, nq, min_scores, k, accept, false)) != OSK_OK) return rc;
+    // the coordinator reduce over the shard lists, as osk_view_search; its total counts the keys the lists
+    // hold, so the exact totals come back beside it and are summed here
+    const MergedOut out(nq, size);
+    OSK_HIP(v->ws_out.reserve(out.total_bytes));
+    const MergedOut::Ptrs o = out.at(v->ws_out.as<char>());
+    OSK_HIP(launch_coord_reduce(v->ws_keys.as<uint64_t>(), v->ws_counts.as<int32_t>(),
+                               v->d_shard_index.as<int32_t>(), nq, 1, S, k, from, size, o.scores, o.docs, o.shard,
+                               o.count, o.total, o.max, st));
+    const size_t o_tot = (out.total_bytes + 7) / 8 * 8, b_tot = sizeof(int64_t) * (size_t)nq * S;
+    OSK_HIP(v->h_stage.reserve(o_tot + b_tot));
+    char* hb = static_cast<char*>(v->h_stage.p);
+    OSK_HIP(hipMemcpyAsync(hb, v->ws_out.p, out.total_bytes, hipMemcpyDeviceToHost, st));
+    OSK_HIP(hipMemcpyAsync(hb + o_tot, v->ws_thr_tot.p, b_tot, hipMemcpyDeviceToHost, st));
+    if ((rc = call.finish()) != OSK_OK) return rc;
+    out.copy_out(hb, out_scores, out_docs, out_shard_index, out_count, out_total_hits, out_max_score);
+    const int64_t* tot = reinterpret_cast<const int64_t*>(hb + o_tot);
+    for (int q = 0; q < nq; ++q) {
+        int64_t sum = 0;
+        for (int s = 0; s < S; ++s) sum += tot[(size_t)q * S + s];
+        out_total_hits[q] = sum;
+    }
+    return OSK_OK;
+    OSK_GUARD_END
+}
+
+int32_t osk_seg_search_threshold_top(osk_seg* seg, const void* queries, int32_t n_queries, const float* min_scores,
+                                     int32_t k, const uint64_t* accept_bits, float* out_scores, int32_t* out_docs,
+                                     int32_t* out_count, int64_t* out_total, int64_t* out_visited) {
+    OSK_GUARD_BEGIN
+    clear_error();
+    OSK_REQUIRE(seg != nullptr && queries != nullptr && min_scores != nullptr, "null argument");
+    OSK_REQUIRE(out_scores && out_docs && out_count && out_total, "null output");
+    int32_t rc = threshold_top_args(n_queries, k);
+    if (rc) return rc;
+    if ((rc = refuse_hamming(seg->sim, "similarity-threshold search")) != OSK_OK) return rc;
+    rc = any_device();
+    if (rc) return rc;
+    rc = check_device(seg->device);
+    if (rc) return rc;
+    osk_view* root;
+    if ((rc = seg_self_view(seg, &root)) != OSK_OK) return rc;
+    (void)hipSetDevice(seg->device);
+    HostCall call;
+    if ((rc = call.begin(root)) != OSK_OK) return rc;
+    osk_view* v = call.v;
+    hipStream_t st = call.st;
+    const int nq = n_queries;
+    const uint64_t* const acc[1] = {accept_bits};
+    if ((rc = threshold_top_shards(v, st, queries, nq, min_scores, k, acc, true)) != OSK_OK) return rc;
+    // keys u64 | totals i64 | visited i64 | counts i32
+    const size_t kb = sizeof(uint64_t) * (size_t)nq * k, tb = sizeof(int64_t) * (size_t)nq, cb = sizeof(int32_t) * nq;
+    OSK_HIP(v->h_stage.reserve(kb + tb + 8 + cb));
+    char* hb = static_cast<char*>(v->h_stage.p);
+    OSK_HIP(hipMemcpyAsync(hb, v->ws_keys.p, kb, hipMemcpyDeviceToHost, st));
+    OSK_HIP(hipMemcpyAsync(hb + kb, v->ws_thr_tot.p, tb, hipMemcpyDeviceToHost, st));
+    OSK_HIP(hipMemcpyAsync(hb + kb + tb, v->ws_visited.p, 8, hipMemcpyDeviceToHost, st));
+    OSK_HIP(hipMemcpyAsync(hb + kb + tb + 8, v->ws_counts.p, cb, hipMemcpyDeviceToHost, st));
+    if ((rc = call.finish()) != OSK_OK) return rc;
+    const uint64_t* keys = reinterpret_cast<const uint64_t*>(hb);
+    const int64_t* tot = reinterpret_cast<const int64_t*>(hb + kb);
+    const int32_t* cnt = reinterpret_cast<const int32_t*>(hb + kb + tb + 8);
+    int64_t visited;
+    std::memcpy(&visited, hb + kb + tb, 8);
+    for (int q = 0; q < nq; ++q) {
+        out_count[q] = cnt[q];
+        out_total[q] = tot[q];
+        for (int i = 0; i < k; ++i) {
+            const uint64_t key = keys[(size_t)q * k + i];
+            const size_t o = (size_t)q * k + i;
+            out_scores[o] = i < cnt[q] ? key_score(key) : -__builtin_inff();
+            out_docs[o] = i < cnt[q] ? key_doc(key) : 0x7FFFFFFF;
+        }
+        if (out_visited) out_visited[q] = visited;
+    }
     return OSK_OK;
     OSK_GUARD_END
 }

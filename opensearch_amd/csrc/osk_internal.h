@@ -364,6 +364,8 @@ struct SelParams {
     int k, sim, dim, units, units8, enc;
     int exact;                       // 1: 64-bit keys of exact scores; 0: int8 bounds LB/UB + exact re-score
     int writer;                      // bounds writer variant (tune sel_writer)
+    int keys_written;                // exact mode: `keys` already holds this query's records (thr_keys_*), so
+                                     // launch_select_one runs no writer of its own (0: it does, the k-NN path)
     const void* q;                   // this query, padded (fp32 UP float4 / int8 16-B units)
     const float* qnorm;              // its |q|² in the device lane order (COSINE)
     const int4* q8;                  // bounds mode: its int8 copy and bound terms
@@ -627,7 +629,8 @@ SelKeysFn sel_keys_ham_fn(int units);
 // ---- similarity-threshold search (osk_threshold.hip): every accepted row with score ≥ min_score ----
 // One corpus pass (thr_scan_*: hit mask words + hit counts per (query, tile, wave)), a prefix sum per
 // (query, shard) (thr_offsets: output offsets, totals, counts, unused slots), an in-order emit
-// (thr_emit_*: re-scores the masked rows).  At most kThrNQ queries share a corpus pass.
+// (thr_emit_*: re-scores the masked rows) — or, for the top-k entries, the same re-score collected by score
+// (thr_top_* / thr_keys_*).  At most kThrNQ queries share a corpus pass.
 constexpr int kThrNQ = 4;
 struct ThrParams {
     const SegDev* segs;
@@ -668,6 +671,14 @@ struct ThrParams {
     int wave_R;                      // rows per wave step of the view's FLOAT32 lane config: a tile is split
                                      // among its waves by it (thr_wave_range), whatever config walks the rows
     int all_maybe;                   // TESTING: every accepted candidate row is a maybe
+    // the top-k collector (thr_top_* / thr_keys_*) in place of the emit: out_docs, out_scores and out_count
+    // are null and cap is 0 then, and thr_offsets writes the totals only
+    int top_k;                       // keys per (query, shard) list; 0 = the positional entries
+    uint64_t* top_cand;              // top_k ≤ kScanMaxK: [n_queries][n_tiles][top_k] tile lists, scan_f32's cand
+    uint64_t* top_keys;              // top_k > kScanMaxK: [view rows] hit keys of the pass's query key_b, 0 = no
+                                     // record (zeroed before): SelParams::keys, sel_keys_*'s contract
+    const int64_t* seg_vrow;         // ...with each segment's first view row (SelParams::seg_vrow)
+    int key_b;
 };
 int thr_words_per_wave(int cfg, int64_t max_tile_rows);
 // Every launcher checks its grid, LDS and arguments and returns hipErrorInvalidValue instead of launching.
@@ -680,6 +691,12 @@ hipError_t launch_thr_scan_sq8(int cfg, const ThrParams& p, hipStream_t s, hipEv
 hipError_t launch_thr_settle(int cfg, const ThrParams& p, hipStream_t s);
 hipError_t launch_thr_offsets(const ThrParams& p, hipStream_t s);
 hipError_t launch_thr_emit(int enc, int cfg, const ThrParams& p, hipStream_t s);
+// The top-k collector over the same mask (top_k ≥ 1): thr_top_* re-scores the pass's masked rows into one
+// best-first list of top_k ≤ kScanMaxK keys per (query, tile) for launch_merge_shards; thr_keys_* stores the
+// hit keys of the pass's query key_b by view row for launch_select_one (SelParams::keys_written), any top_k.
+// Neither compares against min_score: a hit is the mask's.
+hipError_t launch_thr_top(int enc, int cfg, const ThrParams& p, hipStream_t s);
+hipError_t launch_thr_keys(int enc, int cfg, const ThrParams& p, hipStream_t s);
 // ---- nested k-NN (osk_nested.hip): the best accepted child of each parent, then the k best parents ----
 // [L] DiversifyingChildrenFloat/ByteKnnVectorQuery.exactSearch.  One corpus pass (nest_scan_*: scan_f32 /
 // scan_i8 with the wave top-k list replaced by a 64-bit atomic max of the hit key into best[query][parent

@@ -276,6 +276,10 @@ struct osk_view {
     osk::DevBuf ws_thr_mask, ws_thr_wcounts, ws_thr_offsets, ws_thr_min, ws_thr_out;
     osk::DevBuf ws_thr_maybe;              // the int8 first pass's second mask: rows to re-score exactly
     int64_t thr_calls = 0, thr_sq8_calls = 0;   // threshold searches; those that took the int8 first pass
+    // ...and its top-k entries (osk_*_search_threshold_top): calls, those with k > kScanMaxK (the select path's
+    // tail), and the host entries' per-(query, shard) totals; their int8 first passes count in thr_sq8_calls
+    int64_t thr_top_calls = 0, thr_top_sel_calls = 0;
+    osk::DevBuf ws_thr_tot;
     // nested k-NN (osk_nested.hip), built at the first nested search or by osk_view_warm (ensure_nested): each
     // segment's row→parent table and parent-slot base (a shard's parent slots are contiguous), the parent
     // tiles and their shard ranges; the per-pass best-child keys and the parent tiles' candidates
@@ -425,6 +429,12 @@ int32_t view_search_device(osk_view* v, const void* d_queries, int nq, int k, co
 int32_t view_threshold_device(osk_view* v, const void* d_queries, int nq, const float* d_min_scores,
                               const uint64_t* const* d_accept, int cap, int32_t* d_docs, float* d_scores,
                               int32_t* d_count, int64_t* d_total, int64_t* d_visited, hipStream_t st);
+// Per-shard best k of a similarity-threshold search's hits, with the exact totals (caller holds v->mu; device
+// current).  Same key layout as view_search_device.
+int32_t view_threshold_top_device(osk_view* v, const void* d_queries, int nq, const float* d_min_scores, int k,
+                                  const uint64_t* const* d_accept, uint64_t* d_shard_keys,
+                                  int32_t* d_shard_counts, int64_t* d_shard_totals, int64_t* d_visited,
+                                  hipStream_t st);
 // Per-shard nested k-NN on the device: the k best parents, each by its best child (caller holds v->mu;
 // device current).  Same key layout as view_search_device.
 int32_t view_nested_device(osk_view* v, const void* d_queries, int nq, int k, const uint64_t* const* d_accept,

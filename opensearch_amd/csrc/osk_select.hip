@@ -11,6 +11,8 @@
 //                 scores LB/UB (u32 each) of the certified int8 bound (osk_sq8.hip);
 //                 exact mode: the 64-bit hit key (sortable score << 32 | ~doc), the score computed
 //                 with the streaming scan's exact arithmetic (fp32 lane order / exact int32 bytes).
+//                 SelParams::keys_written: the caller wrote the keys itself (the threshold collector's
+//                 thr_keys_*: a key per hit, 0 elsewhere) and no writer runs here.
 //   radix       per shard, T = the k-th largest LB (3 passes of 11-bit digits) or the k-th largest
 //               key (6 passes): LDS histograms
 //               per tile, global per-shard histograms, one wave picks the digit (RadixState).  A shard
@@ -833,7 +835,9 @@ hipError_t launch_select_one(const SelParams& p, int cfg, hipStream_t s, hipEven
                                                    : kSelKeysF32[cfg][p.sim == SIM_EUCLIDEAN ? 1 : 0])
                            : kSelBounds[sel_bounds_cfg(p.units8)][p.writer & 3][p.accept ? 1 : 0];
     if (!writer || (p.sim == SIM_HAMMING && !p.exact)) return hipErrorInvalidValue;
-    if (ev_start || ev_stop)
+    if (p.keys_written) {   // the caller's kernels wrote `keys` (the threshold collector): select on them as they are
+        if (!p.exact || !p.keys || ev_start || ev_stop) return hipErrorInvalidValue;
+    } else if (ev_start || ev_stop)
         hipExtLaunchKernelGGL(writer, tg, tb, 0, s, ev_start, ev_stop, 0, p);
     else
         hipLaunchKernelGGL(writer, tg, tb, 0, s, p);

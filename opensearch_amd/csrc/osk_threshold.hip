@@ -19,6 +19,11 @@
 //   thr_emit_f32 / thr_emit_i8   per (query, tile, wave): walk the mask words and re-score each set bit's
 //                                row with the same function (L lanes per row); doc + score go to
 //                                offset + rank when that is < cap.  The hit decision is the mask's.
+//   thr_top_f32 / thr_top_i8     the osk_*_search_threshold_top entries, in place of the emit: the same walk,
+//                                each hit's key offered to the scans' wave list → the best k ≤ 64 per (query,
+//                                tile) in scan_f32's cand layout → merge_shards.  thr_offsets writes the totals.
+//   thr_keys_f32 / thr_keys_i8   ...for 64 < k ≤ OSK_MAX_K: each hit's key stored by view row, the select
+//                                path's exact-key records → launch_select_one without its own writer.
 //
 // Mask word ownership: a wave's row range is a multiple of R = 64/L rows, not of 64, and under a filter
 // on a dense field the walk visits compacted rows — so every wave owns `wpw` words of its own
@@ -579,8 +584,9 @@ __global__ __launch_bounds__(kBlock) void thr_offsets(ThrParams p) {
     const long long cnt = carry < (long long)p.cap ? carry : (long long)p.cap;
     if (tid == 0) {
         p.out_total[o] = carry;
-        p.out_count[o] = (int32_t)cnt;
+        if (p.out_count) p.out_count[o] = (int32_t)cnt;
     }
+    if (!p.out_docs) return;   // the top-k collector: no positional output (its lists carry their own zeros)
     // unused slots, as osk_seg_search leaves them
     for (int64_t i = cnt + tid; i < p.cap; i += kBlock) {
         p.out_docs[o * p.cap + i] = 0x7FFFFFFF;
@@ -678,6 +684,137 @@ __global__ __launch_bounds__(kBlock) void thr_emit_i8(ThrParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// collect: the best hits by score instead of all of them by position.  The emit's walk — a wave visits
+// exactly its own mask's rows and re-scores them with the scan's functions, so the score bits are the k-NN
+// entries' — with each hit's key make_key(score, doc_base + doc) going to `sink(key, row, owner)`: every
+// lane calls it, key is 0 in the lanes past the step's rows and `owner` holds in one lane per row group.
+// A wave without hits does no loads.  No comparison against min_score: a hit is the mask's decision.
+// ------------------------------------------------------------------------------------------------
+template <int L, int V, bool L2K, class Sink>
+__device__ __forceinline__ void thr_hit_keys_f32(const ThrParams& p, int b, size_t wi, const TileDev& tile,
+                                                 const SegDev& seg, int wave, int lane, Sink&& sink) {
+    constexpr int R = 64 / L;
+    constexpr int UP = L * V;
+    const int t = lane & (L - 1), g = lane / L;
+    const float4* __restrict__ X = static_cast<const float4*>(seg.rows);
+    const float4* __restrict__ Q = static_cast<const float4*>(p.q) + (size_t)b * UP;
+    const int units = p.units, sim = p.sim;
+    float4 qf[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) qf[j] = Q[t + j * L];
+    auto qat = [&](int j) -> float4 { return qf[j]; };
+    float qn = 0.0f;
+    if (!L2K && sim == SIM_COSINE) qn = thr_qnorm_f32<L, V>(qat);
+    int64_t wb, we;
+    thr_wave_range<R>(tile, wave, wb, we);
+    walk_rows<R>(0, we - wb, p.mask + wi * p.wpw, nullptr, lane, g, [&](const int64_t rel, bool valid, bool) {
+        const int64_t row = wb + rel;
+        float4 xv[V];
+        thr_load_row_f32<L, V, false>(X + row * units, valid, units, t, xv);
+        float xn = 0.0f;
+        if (!L2K && sim == SIM_COSINE && valid) xn = seg.xnorm_f[row];
+        const float sc = thr_score_f32<L, V, L2K>(xv, qat, sim, qn, xn);
+        uint64_t key = 0ull;
+        if (valid) {
+            const int32_t doc = seg.ord_to_doc ? seg.ord_to_doc[row] : (int32_t)row;
+            key = make_key(sc, (uint32_t)(seg.doc_base + doc));
+        }
+        sink(key, row, t == 0);
+    });
+}
+
+template <int L, int V, class Sink>
+__device__ __forceinline__ void thr_hit_keys_i8(const ThrParams& p, int b, size_t wi, const TileDev& tile,
+                                                const SegDev& seg, int wave, int lane, Sink&& sink) {
+    constexpr int R = 64 / L;
+    constexpr int UP = L * V;
+    const int t = lane & (L - 1), g = lane / L;
+    const int4* __restrict__ X = static_cast<const int4*>(seg.rows);
+    const int4* __restrict__ Q = static_cast<const int4*>(p.q) + (size_t)b * UP;
+    const int units = p.units, sim = p.sim, dim = p.dim;
+    int4 qf[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) qf[j] = Q[t + j * L];
+    auto qat = [&](int j) -> int4 { return qf[j]; };
+    const int32_t qn = thr_qnorm_i8<L, V>(qat);
+    int64_t wb, we;
+    thr_wave_range<R>(tile, wave, wb, we);
+    walk_rows<R>(0, we - wb, p.mask + wi * p.wpw, nullptr, lane, g, [&](const int64_t rel, bool valid, bool) {
+        const int64_t row = wb + rel;
+        int4 xv[V];
+        thr_load_row_i8<L, V>(X + row * units, valid, units, t, xv);
+        const int32_t xn = valid ? seg.xnorm_i[row] : 0;
+        const float sc = thr_score_i8<L, V>(xv, qat, sim, qn, xn, dim);
+        uint64_t key = 0ull;
+        if (valid) {
+            const int32_t doc = seg.ord_to_doc ? seg.ord_to_doc[row] : (int32_t)row;
+            key = make_key(sc, (uint32_t)(seg.doc_base + doc));
+        }
+        sink(key, row, t == 0);
+    });
+}
+
+// top: one workgroup per (tile, query of the pass), k ≤ kScanMaxK.  Each wave keeps the best k of its hits in
+// lanes 0..k-1 (the scans' wave list), the four lists are folded by wave 0 and stored as the tile's list
+// in scan_f32's cand layout — all k slots, zeros past the hits: the buffer is not cleared.
+// F32: thr_hit_keys_f32<L, V, L2K>; else thr_hit_keys_i8<L, V> (L2K unused).
+template <int L, int V, bool L2K, bool F32>
+__device__ __forceinline__ void thr_top_tile(const ThrParams& p) {
+    __shared__ uint64_t slist[4 * 64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = blockIdx.y, k = p.top_k;
+    const size_t wi = ((size_t)b * p.n_tiles + blockIdx.x) * 4 + wave;
+    uint64_t lk = 0ull, thr = 0ull;
+    if (__builtin_amdgcn_readfirstlane(p.counts[wi]) != 0) {   // (wave-uniform; every wave reaches the barrier)
+        const TileDev tile = p.tiles[blockIdx.x];
+        const SegDev seg = p.segs[tile.seg];
+        auto offer = [&](uint64_t key, int64_t, bool owner) { wave_offer(key, owner, lk, thr, lane, k); };
+        if constexpr (F32) thr_hit_keys_f32<L, V, L2K>(p, b, wi, tile, seg, wave, lane, offer);
+        else thr_hit_keys_i8<L, V>(p, b, wi, tile, seg, wave, lane, offer);
+    }
+    slist[wave * 64 + lane] = lane < k ? lk : 0ull;
+    __syncthreads();
+    if (wave == 0) {
+        block_fold(slist, lk, thr, lane, k);
+        if (lane < k) p.top_cand[((size_t)(p.q0 + b) * p.n_tiles + blockIdx.x) * k + lane] = lk;
+    }
+}
+template <int L, int V, bool L2K>
+__global__ __launch_bounds__(kBlock) void thr_top_f32(ThrParams p) {
+    thr_top_tile<L, V, L2K, true>(p);
+}
+template <int L, int V>
+__global__ __launch_bounds__(kBlock) void thr_top_i8(ThrParams p) {
+    thr_top_tile<L, V, false, false>(p);
+}
+
+// keys: one workgroup per tile, the pass's query key_b, any k.  Each hit's key goes to its view row's slot
+// of the select path's exact-key records (zeroed by the host before: every other row stays "no record").
+template <int L, int V, bool L2K, bool F32>
+__device__ __forceinline__ void thr_keys_tile(const ThrParams& p) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int b = p.key_b;
+    const size_t wi = ((size_t)b * p.n_tiles + blockIdx.x) * 4 + wave;
+    if (__builtin_amdgcn_readfirstlane(p.counts[wi]) == 0) return;
+    const TileDev tile = p.tiles[blockIdx.x];
+    const SegDev seg = p.segs[tile.seg];
+    uint64_t* keys = p.top_keys + p.seg_vrow[tile.seg];
+    auto store = [&](uint64_t key, int64_t row, bool owner) {
+        if (owner && key != 0ull) keys[row] = key;
+    };
+    if constexpr (F32) thr_hit_keys_f32<L, V, L2K>(p, b, wi, tile, seg, wave, lane, store);
+    else thr_hit_keys_i8<L, V>(p, b, wi, tile, seg, wave, lane, store);
+}
+template <int L, int V, bool L2K>
+__global__ __launch_bounds__(kBlock) void thr_keys_f32(ThrParams p) {
+    thr_keys_tile<L, V, L2K, true>(p);
+}
+template <int L, int V>
+__global__ __launch_bounds__(kBlock) void thr_keys_i8(ThrParams p) {
+    thr_keys_tile<L, V, false, false>(p);
+}
+
+// ------------------------------------------------------------------------------------------------
 // dispatch: the scans' lane configs × NQ ∈ {1, kThrNQ} × {L2, dot-family} × {plain, non-temporal}
 // ------------------------------------------------------------------------------------------------
 using ThrFn = void (*)(ThrParams);
@@ -717,13 +854,36 @@ int thr_sq8_cfg(int u8) {
     return u8 <= 4 ? 0 : u8 <= 8 ? 1 : u8 <= 16 ? 2 : u8 <= 32 ? 3 : u8 <= 48 ? 4 : u8 <= 64 ? 5 : u8 <= 128 ? 6 : 7;
 }
 
+// the collector over the pass's mask, by lane config: {L2, dot-family} for float32
+#define OSK_THR_TOP(L, V) {thr_top_f32<L, V, true>, thr_top_f32<L, V, false>}
+#define OSK_THR_KEYS(L, V) {thr_keys_f32<L, V, true>, thr_keys_f32<L, V, false>}
+const ThrFn kThrTopF32[9][2] = {OSK_THR_TOP(4, 2),  OSK_THR_TOP(8, 2),  OSK_THR_TOP(8, 4),
+                                OSK_THR_TOP(16, 4), OSK_THR_TOP(16, 8), OSK_THR_TOP(16, 12),
+                                OSK_THR_TOP(32, 8), OSK_THR_TOP(64, 8), OSK_THR_TOP(64, 16)};
+const ThrFn kThrTopI8[9] = {thr_top_i8<4, 2>,  thr_top_i8<8, 2>,  thr_top_i8<8, 4>,
+                            thr_top_i8<16, 4>, thr_top_i8<16, 8>, thr_top_i8<16, 12>,
+                            thr_top_i8<32, 8>, thr_top_i8<64, 8>, thr_top_i8<64, 16>};
+const ThrFn kThrKeysF32[9][2] = {OSK_THR_KEYS(4, 2),  OSK_THR_KEYS(8, 2),  OSK_THR_KEYS(8, 4),
+                                 OSK_THR_KEYS(16, 4), OSK_THR_KEYS(16, 8), OSK_THR_KEYS(16, 12),
+                                 OSK_THR_KEYS(32, 8), OSK_THR_KEYS(64, 8), OSK_THR_KEYS(64, 16)};
+const ThrFn kThrKeysI8[9] = {thr_keys_i8<4, 2>,  thr_keys_i8<8, 2>,  thr_keys_i8<8, 4>,
+                             thr_keys_i8<16, 4>, thr_keys_i8<16, 8>, thr_keys_i8<16, 12>,
+                             thr_keys_i8<32, 8>, thr_keys_i8<64, 8>, thr_keys_i8<64, 16>};
+
+// a pass's outputs: the positional entries' four arrays and a capacity, or (top_k ≥ 1) the totals alone
+bool thr_out_ok(const ThrParams& p) {
+    if (p.top_k == 0) return p.cap >= 1 && p.out_docs && p.out_scores && p.out_count && p.out_total;
+    return p.top_k >= 1 && p.cap == 0 && !p.out_docs && !p.out_scores && !p.out_count &&
+           p.out_total;
+}
+
 // what every launch of a pass must satisfy; anything else is refused, never guessed
 bool thr_params_ok(int enc, int cfg, const ThrParams& p) {
     return (enc == ENC_FLOAT32 || enc == ENC_BYTE) && cfg >= 0 && cfg < 9 && p.sim >= 0 && p.sim <= 3 &&
-           p.q_count >= 1 && p.q_count <= kThrNQ && p.n_shards >= 1 && p.cap >= 1 &&
+           p.q_count >= 1 && p.q_count <= kThrNQ && p.n_shards >= 1 &&
            p.wpw >= 1 && p.n_tiles >= 0 && p.units >= 1 && p.units <= cfg_padded_units(cfg) &&
            p.segs && p.tiles && p.q && p.min_score && p.mask && p.counts && p.offsets && p.shard_tile_begin &&
-           p.out_docs && p.out_scores && p.out_count && p.out_total;
+           thr_out_ok(p);
 }
 
 }  // namespace
@@ -782,17 +942,37 @@ hipError_t launch_thr_settle(int cfg, const ThrParams& p, hipStream_t s) {
 }
 
 hipError_t launch_thr_offsets(const ThrParams& p, hipStream_t s) {
-    if (p.q_count < 1 || p.q_count > kThrNQ || p.n_shards < 1 || p.cap < 1 || p.n_tiles < 0 || !p.counts ||
-        !p.offsets || !p.shard_tile_begin || !p.out_docs || !p.out_scores || !p.out_count || !p.out_total)
+    if (p.q_count < 1 || p.q_count > kThrNQ || p.n_shards < 1 || p.n_tiles < 0 || !p.counts || !p.offsets ||
+        !p.shard_tile_begin || !thr_out_ok(p))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(thr_offsets, dim3(p.n_shards, p.q_count), dim3(kBlock), 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_thr_emit(int enc, int cfg, const ThrParams& p, hipStream_t s) {
-    if (!thr_params_ok(enc, cfg, p) || p.n_tiles < 1) return hipErrorInvalidValue;
+    // (top_k == 0: the positional outputs are there; the collector's form of the parameters has none)
+    if (!thr_params_ok(enc, cfg, p) || p.n_tiles < 1 || p.top_k != 0) return hipErrorInvalidValue;
     const ThrFn fn = enc == ENC_FLOAT32 ? kThrEmitF32[cfg][p.sim == SIM_EUCLIDEAN ? 0 : 1] : kThrEmitI8[cfg];
     hipLaunchKernelGGL(fn, dim3(p.n_tiles, p.q_count), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
+}
+
+// thr_emit's grid; the wave lists hold top_k ≤ kScanMaxK keys and the fold's LDS is static (4 lists of 64)
+hipError_t launch_thr_top(int enc, int cfg, const ThrParams& p, hipStream_t s) {
+    if (!thr_params_ok(enc, cfg, p) || p.n_tiles < 1 || p.top_k < 1 || p.top_k > kScanMaxK || !p.top_cand)
+        return hipErrorInvalidValue;
+    const ThrFn fn = enc == ENC_FLOAT32 ? kThrTopF32[cfg][p.sim == SIM_EUCLIDEAN ? 0 : 1] : kThrTopI8[cfg];
+    hipLaunchKernelGGL(fn, dim3(p.n_tiles, p.q_count), dim3(kBlock), 0, s, p);
+    return hipGetLastError();
+}
+
+// one query of the pass (key_b) over every tile
+hipError_t launch_thr_keys(int enc, int cfg, const ThrParams& p, hipStream_t s) {
+    if (!thr_params_ok(enc, cfg, p) || p.n_tiles < 1 || p.top_k < 1 || !p.top_keys || !p.seg_vrow || p.key_b < 0 ||
+        p.key_b >= p.q_count)
+        return hipErrorInvalidValue;
+    const ThrFn fn = enc == ENC_FLOAT32 ? kThrKeysF32[cfg][p.sim == SIM_EUCLIDEAN ? 0 : 1] : kThrKeysI8[cfg];
+    hipLaunchKernelGGL(fn, dim3(p.n_tiles), dim3(kBlock), 0, s, p);
     return hipGetLastError();
 }
 

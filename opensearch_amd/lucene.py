@@ -252,6 +252,23 @@ class GpuFlatVectorsReader:
                                              ptr(count), ptr(total), ptr(visited)))
         return docs, scores, count, total, visited
 
+    def search_threshold_top(self, targets, min_score, k: int, accept_bits: np.ndarray | None = None):
+        """The best k of the accepted vectors scoring ≥ min_score (one per target, or a scalar for all), by score
+        descending then doc ascending, in search_batch's layout, with the exact number of matches:
+        (scores[nq,k], docs[nq,k], count[nq], total[nq], visited[nq]) — osk_seg_search_threshold_top."""
+        q = _as_query_array(targets, self.encoding, self.dim)
+        nq = q.shape[0]
+        ms = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32), (nq,)))
+        scores = np.empty((nq, max(k, 1)), np.float32)   # (a bad k is the library's to refuse)
+        docs = np.empty((nq, max(k, 1)), np.int32)
+        count = np.empty(nq, np.int32)
+        total = np.empty(nq, np.int64)
+        visited = np.empty(nq, np.int64)
+        ab = None if accept_bits is None else np.ascontiguousarray(accept_bits, dtype=np.uint64)
+        check(lib().osk_seg_search_threshold_top(self.handle, ptr(q), nq, ptr(ms), k, ptr(ab), ptr(scores), ptr(docs),
+                                                 ptr(count), ptr(total), ptr(visited)))
+        return scores, docs, count, total, visited
+
     def set_parents(self, parent_mask) -> None:
         """Register the leaf's parent docs ([L] the nested path's BitSetProducer, cached per segment):
         parent_mask is bool[max_doc].  Once per segment — the same mask again is a no-op, another one raises."""
@@ -602,6 +619,25 @@ class _GpuVectorSimilarityQuery(_VectorSimilarityQuery):
         n = int(c[0, 0])
         return TopDocs(TotalHits(int(t[0, 0])), [ScoreDoc(int(d[0, 0, i]), float(s[0, 0, i])) for i in range(n)])
 
+    def top_docs(self, leaves: Iterable[LeafReaderContext], n: int) -> TopDocs:
+        """What the shard's TopScoreDocCollector keeps of this query (numDocs = n): the best n matches by score
+        descending, doc ascending, and totalHits = every match — ONE osk_view_search_threshold_top call over the
+        cached view, instead of `rewrite` (every match brought to the host) and a sort.  1 ≤ n ≤ OSK_MAX_K."""
+        leaves = [lf for lf in leaves if lf.reader.field == self.field]
+        if not leaves:
+            return TopDocs(TotalHits(0, Relation.EQUAL_TO), [])
+        G = _GpuKnnVectorQuery
+        e = G._acquire_view(self, leaves)
+        try:
+            accept = [self._accept(lf) for lf in leaves]
+            if all(a is None for a in accept):
+                accept = None
+            s, d, _, c, t, _ = e.view.search_threshold_top(self.target, self.result_similarity, n, 0, n, accept)
+        finally:
+            G._release_view(e)
+        hits = [ScoreDoc(int(d[0, i]), float(s[0, i])) for i in range(int(c[0]))]
+        return TopDocs(TotalHits(int(t[0]), Relation.EQUAL_TO), hits)
+
 
 class GpuFloatVectorSimilarityQuery(_GpuVectorSimilarityQuery):
     encoding = VectorEncoding.FLOAT32
@@ -718,7 +754,11 @@ def shard_similarity_query_phase(query: _VectorSimilarityQuery, leaves: Sequence
                                  size: int) -> TopDocs:
     """The shard's query phase for a similarity query: a TopScoreDocCollector over the query's scorer with
     numDocs = from+size (S/search/query/TopDocsCollectorContext.java:866-891) — hits by score desc, doc asc,
-    cut to from+size; totalHits = every match (EQUAL_TO).  (max_score = score_docs[0].score when there is one.)"""
+    cut to from+size; totalHits = every match (EQUAL_TO).  (max_score = score_docs[0].score when there is one.)
+    The plugin's query classes collect on the device (top_docs: one call) while the window fits a device list,
+    1 ≤ from+size ≤ OSK_MAX_K; the CPU mirror classes, and any larger window, rewrite and sort here."""
+    if isinstance(query, _GpuVectorSimilarityQuery) and 1 <= from_ + size <= _lib.OSK_MAX_K:
+        return query.top_docs(leaves, from_ + size)
     matched = query.rewrite(leaves)
     hits = sorted(matched.score_docs, key=lambda h: (-h.score, h.doc))[: from_ + size]
     return TopDocs(TotalHits(matched.total_hits.value, Relation.EQUAL_TO), [ScoreDoc(h.doc, h.score) for h in hits])
@@ -845,6 +885,25 @@ class DeviceShardSet:
                                               ptr(count), ptr(total)))
         return docs, scores, count, total
 
+    def search_threshold_top(self, targets, min_score, k: int, from_: int = 0, size: int = 10, accept=None):
+        """Each shard's best k of the accepted vectors scoring ≥ min_score (one per target, or a scalar), then the
+        coordinator merge — osk_view_search_threshold_top; `search`'s outputs, except that total[q] is the exact
+        number of matches over all shards, whatever k, and mx[q] the best match's score (NaN when none)."""
+        q = _as_query_array(targets, self.encoding, self.dim)
+        nq = q.shape[0]
+        ms = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32), (nq,)))
+        scores = np.empty((nq, max(size, 1)), np.float32)   # (a bad size is the library's to refuse)
+        docs = np.empty((nq, max(size, 1)), np.int32)
+        shard = np.empty((nq, max(size, 1)), np.int32)
+        count = np.empty(nq, np.int32)
+        total = np.empty(nq, np.int64)
+        mx = np.empty(nq, np.float32)
+        keep: list = []
+        acc_arr = self._accept_table(accept, keep)
+        check(lib().osk_view_search_threshold_top(self.handle, ptr(q), nq, ptr(ms), k, from_, size, acc_arr,
+                                                  ptr(scores), ptr(docs), ptr(shard), ptr(count), ptr(total), ptr(mx)))
+        return scores, docs, shard, count, total, mx
+
     def stats(self) -> tuple[int, int]:
         """(searches that took the batched MFMA path, queries recomputed after a failed certificate)."""
         a, b = C.c_int64(), C.c_int64()
@@ -854,7 +913,8 @@ class DeviceShardSet:
     def counter(self, name: str) -> int:
         """A named counter of the view (osk_view_counter): "sq8_calls", "sq8_fallback_queries",
         "sq8_rescored_rows", "mfma_calls", "mfma_fallback_queries", "threshold_calls", "threshold_sq8_calls",
-        "threshold_sq8_settled_rows", "nested_calls", "nested_sq8_calls" (nested searches that took the int8 first pass),
+        "threshold_sq8_settled_rows", "threshold_top_calls", "threshold_top_select_calls" (the top-k threshold
+        entries' calls, and those with k > 64), "nested_calls", "nested_sq8_calls" (nested searches that took the int8 first pass),
         "nested_sq8_settled_rows" (rows their settle re-scored exactly)."""
         v = C.c_int64()
         check(lib().osk_view_counter(self.handle, name.encode(), C.byref(v)))
